@@ -7,13 +7,18 @@ config.toml:189-195) per GPU, models.distmod with 30 phosphosites (S = 32), y0 =
 written to HBM + the fused Morris scalar per replica, then -- for N > 1 -- ONE all-gather (RCCL) of the per-replica scalars.
 Inputs are resident in HBM before the timed region.  Weak scaling: every rank owns its own 65 536 replicas.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]      (N > 1: under torch.distributed.run, one rank per GPU)
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline`, `cpu_baseline` and `parity`.
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]      (N > 1: under torch.distributed.run, one rank per GPU)
+Prints ONE JSON line on rank 0: `metric`, `value` (replicas/s over the K timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+(wall milliseconds of one timed step), the solver's step counts and the `roofline` / `roofline_fp64` figures of the timed kernel.
 
-Order of work on rank 0 at N = 1: (1) the CPU legs (cpu_baseline, cpu_same_algorithm, the single-call CPU latency) run FIRST, before this
-process makes its first GPU call -- they fork worker pools, and HIP does not support fork() after initialisation; (2) the timed region;
-(3) secondary, untimed-for-the-metric legs: peaks measured on this box, BASELINE config 1 as the reference runs it (one theta per call),
-BASELINE config 5's network path at the optimiser's tolerance, the other per-protein sizes.
+A plain run does only what that line needs: set up, warm up, time EXACTLY K steps, write the outputs (--dump-outputs), print.
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as float64 DIR/<name>.npy (see dump_outputs).
+--full adds everything else, in this order on rank 0 at N = 1: (1) the CPU legs (cpu_baseline, cpu_same_algorithm, the single-call CPU
+latency) run FIRST, before this process makes its first GPU call -- they fork worker pools, and HIP does not support fork() after
+initialisation; (2) the timed region; (3) `parity` of the first 64 replicas against the committed SciPy trajectories; (4) secondary,
+untimed-for-the-metric legs: peaks measured on this box, BASELINE config 1 as the reference runs it (one theta per call), BASELINE
+config 5's network path at the optimiser's tolerance, the other per-protein sizes.  --no-cpu-baseline / --no-network / --no-secondary
+trim a --full run; --only-network (with --full) prints the network leg alone.
 """
 from __future__ import annotations
 
@@ -114,6 +119,46 @@ def wait_for_library(lib_path: Path, local_rank: int):
         time.sleep(1.0)
 
 
+DUMP_SOL_REPLICAS = 8192          # sol[., 14, 32] f64 of this many replicas: 29.4 MB
+DUMP_VEC_REPLICAS = 1 << 18       # per-replica vectors (metric, status, n_steps: 32 B per replica) of at most this many: 8.4 MB
+
+
+def _dump_sample(n: int, k: int, salt: int):
+    """All of range(n) when k >= n, else a fixed, seeded, sorted sample of k of them (the same for every run at the same n)."""
+    if k >= n:
+        return None
+    return np.sort(np.random.default_rng(20260515 + salt).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirpath: Path, res, gathered=None) -> None:
+    """What the timed path handed its caller in the LAST timed step, as float64 .npy files under dirpath (under 64 MB in all):
+      metric.npy [B]             the fused Morris total_signal per replica
+      status.npy [B]             solver status per replica (0 = ok)
+      n_steps.npy [B, 2]         accepted / rejected steps per replica
+      sol.npy [Bs, 14, 32]       the clipped trajectories of a fixed seeded sample of DUMP_SOL_REPLICAS replicas (sol_replicas.npy: which)
+      metric_gathered.npy        under the collective: the all-gathered scalars of every rank
+    Batches above DUMP_VEC_REPLICAS write the per-replica vectors on a fixed seeded sample of that size (vec_replicas.npy: which)."""
+    dirpath.mkdir(parents=True, exist_ok=True)
+    B = res.metric.shape[0]
+
+    def save(name, t, idx):
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(dirpath / f"{name}.npy", t.detach().to(torch.float64).cpu().numpy())
+
+    iv = _dump_sample(B, DUMP_VEC_REPLICAS, 12)
+    save("metric", res.metric, iv)
+    save("status", res.status, iv)
+    save("n_steps", res.n_steps, iv)
+    if iv is not None:
+        np.save(dirpath / "vec_replicas.npy", iv.astype(np.float64))
+    isol = _dump_sample(B, DUMP_SOL_REPLICAS, 11)
+    save("sol", res.sol, isol)
+    np.save(dirpath / "sol_replicas.npy", (np.arange(B) if isol is None else isol).astype(np.float64))
+    if gathered is not None:
+        save("metric_gathered", gathered, _dump_sample(gathered.shape[0], DUMP_VEC_REPLICAS, 13))
+
+
 def cpu_legs(args, theta_h, n_sites, S):
     """Runs BEFORE the first GPU call of this process (fork-based worker pools)."""
     from oracle import protein_models as pm
@@ -157,13 +202,19 @@ def main():
     ap.add_argument("--atol", type=float, default=None, help="default: rtol / 100")
     ap.add_argument("--linsolve", default="auto")
     ap.add_argument("--method", default="lrp12")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-network", action="store_true", help="skip the network-path leg (BASELINE config 5)")
-    ap.add_argument("--no-secondary", action="store_true", help="only the metric line (profiling runs)")
-    ap.add_argument("--only-network", action="store_true", help="only the network leg, printed as its own JSON line (one workload per rocprof profile)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baselines, the parity check and the secondary legs (off: the metric line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
+    ap.add_argument("--no-network", action="store_true", help="--full without the network-path legs (BASELINE configs 4, 5)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary legs (profiling runs)")
+    ap.add_argument("--only-network", action="store_true", help="with --full: only the network leg, printed as its own JSON line (one workload per rocprof profile)")
     ap.add_argument("--no-ramp", action="store_true", help="skip the untimed clock-ramp launches before the warm-up steps")
     ap.add_argument("--cpu-sample", type=int, default=0, help="replicas in the CPU baseline sample (0 = 128 per core)")
     args = ap.parse_args()
+    if args.only_network and not args.full:
+        ap.error("--only-network is part of --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -183,7 +234,7 @@ def main():
 
     # ---- (1) CPU legs: before the first GPU call of this process
     cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.only_network:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.only_network:
         cpu = cpu_legs(args, theta_h, n_sites, S)
 
     torch.cuda.set_device(local_rank)
@@ -277,6 +328,9 @@ def main():
     nst = out.n_steps.double().mean(dim=0).tolist()
     assert gathered.shape[0] == B * world
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), outs[(counter[0] - 1) % len(outs)], gathered if use_dist else None)
+
     if rank == 0:
         total_replicas = B * world * args.steps
         value = total_replicas / elapsed
@@ -327,7 +381,7 @@ def main():
                                      "note": "instruction counts from the committed profile %s, kernel time from this run; 1024 SIMDs, ~2.1 GHz under FP64 load" % prof[-1].name}
         # parity on the first 64 replicas of this very batch against the committed SciPy reference trajectories
         gfile = ROOT / "tests" / "golden" / "protein_distmod_n30_c3bounds.npz"
-        if gfile.exists() and args.method in ("rodas4", "lrp8", "lrp12") and B >= 64:
+        if args.full and gfile.exists() and args.method in ("rodas4", "lrp8", "lrp12") and B >= 64:
             g = np.load(gfile)
             if np.array_equal(g["theta"], theta_h[:64]):
                 sol64 = out.sol[:64].cpu().numpy()
@@ -340,7 +394,7 @@ def main():
         for k in ("cpu_baseline", "cpu_same_algorithm"):
             if k in cpu:
                 res[k] = cpu[k]
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             res.update(secondary_legs(args, dev, tt, cpu))
             if res.get("peaks_measured", {}).get("fp64_fma_tflops", 0) > 0:
                 res["roofline_fp64"]["frac_of_measured_peak"] = res["roofline_fp64"]["achieved"] / res["peaks_measured"]["fp64_fma_tflops"]

@@ -92,18 +92,28 @@ def test_nccl_world_size_one_drives_every_sharded_driver(tmp_path):
     assert r.returncode == 0 and "CHILD_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
 
 
-def test_bench_collective_path_at_world_size_one():
+def test_bench_collective_path_at_world_size_one(tmp_path):
     """bench.py exactly as the driver launches it for N > 1 (RANK / WORLD_SIZE / MASTER_* in the environment), at world size 1 with the
-    collective forced: the all-gather on its own HIP stream, the barrier and the max-over-ranks timing all execute."""
+    collective forced: the all-gather on its own HIP stream, the barrier and the max-over-ranks timing all execute.  --dump-outputs
+    writes what the last timed step computed, the gathered scalars included."""
     env = dict(os.environ)
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), PK_FORCE_COLLECTIVE="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-secondary"],
-                       capture_output=True, text=True, timeout=900, env=env)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-secondary",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 1 and "all-gather" in line["config"]["workload"] and line["value"] > 1e6
     assert line["solver"]["flagged_replicas"] == 0 and line["parity"]["max_band_err_vs_scipy_tight"] <= 0.1
+    assert line["steps"] == 20 and line["ms_per_step"] > 0
+    import numpy as np
+    files = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+    assert {"metric", "status", "n_steps", "sol", "sol_replicas", "metric_gathered"} <= set(files)
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(f.stat().st_size for f in dump.glob("*.npy")) <= 64 << 20
+    B = files["metric"].shape[0]
+    assert B == 65536 and files["sol"].shape == (8192, 14, 32) and files["n_steps"].shape == (B, 2)
+    assert np.array_equal(files["metric_gathered"], files["metric"]) and not files["status"].any() and np.isfinite(files["sol"]).all()
 
 
 CHILD2 = r'''

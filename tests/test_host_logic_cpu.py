@@ -62,49 +62,32 @@ def test_solver_opts_kernel_field_roundtrip(built_lib):
         _capi.default_opts(kernel="warp")
 
 
-_REF_SCRIPT = r'''
-import sys, pathlib, numpy as np, pandas as pd
-repo = pathlib.Path(sys.argv[1]); out = sys.argv[2]; model_name = sys.argv[3]
-sys.path.insert(0, str(repo / "tools"))
-import make_golden_network as mg
-mods, tmp = mg.import_reference(model_name)
-cfg, net, bm = mods["config"], mods["network"], mods["buildmat"]
-rng = np.random.default_rng(31 + 100 * cfg.MODEL)                      # the network of tools/make_golden_pins.py main_network
-prots, kinases, inter, tf_net = mg.synth_frames(rng, 8, 3, 2, 2, 10)
-idx = net.Index(inter, tf_interactions=tf_net, kin_beta_map={k: float(rng.uniform(0.5, 1.5)) for k in kinases}, tf_beta_map={})
-grid = np.asarray(cfg.TIME_POINTS_PROTEIN, float)
-rows = []
-for k in idx.kinases:
-    base = 1.0 + 0.5 * np.sin(rng.uniform(0, 6) + np.arange(grid.size) * rng.uniform(0.2, 0.8))
-    for t, v in zip(grid, base):
-        rows.append(dict(protein=k, time=float(t), fc=float(max(v, 1e-6))))
-kin_in = net.KinaseInput(idx.kinases, pd.DataFrame(rows))
-W = bm.build_W_parallel(inter, idx, n_cores=1)
-tf_mat = bm.build_tf_matrix(tf_net, idx, tf_beta_map={}, kin_beta_map={})
-tf_deg = np.asarray(np.abs(tf_mat).sum(axis=1)).ravel().astype(np.float64); tf_deg[tf_deg < 1e-12] = 1.0
-d = dict(c_k=np.ones(len(idx.kinases)), A_i=np.ones(idx.N), B_i=np.full(idx.N, 0.2), C_i=np.full(idx.N, 0.5), D_i=np.full(idx.N, 0.05),
-         Dp_i=np.full(idx.total_sites, 0.05), E_i=np.ones(idx.N), tf_scale=0.1)
-sysm = net.System(idx, W, tf_mat, kin_in, d, tf_deg)
-sys.path.insert(0, str(repo))
-from phoskintime_amd.global_model.engine import NetworkEngine
-np.savez(out, **NetworkEngine.desc_from_system(sysm))
-'''
+def _reference_system(g):
+    """The attributes a reference ``global_model.network.System`` holds, as stored by tools/make_golden_from_system.py (which runs the
+    reference's own Index / build_W_parallel / build_tf_matrix / System on the seeded network of tools/make_golden_pins.py), rebuilt
+    with the reference's types: Python dicts for the index maps, arrays in the dtypes the reference keeps."""
+    idx = types.SimpleNamespace(N=int(g["N"]), kinases=[str(k) for k in g["kinases"]],
+                                p2i={str(k): int(v) for k, v in zip(g["p2i_keys"], g["p2i_values"])},
+                                k2i={str(k): int(v) for k, v in zip(g["k2i_keys"], g["k2i_values"])},
+                                offset_y=g["offset_y"], offset_s=g["offset_s"], n_sites=g["n_sites"])
+    if bool(g["has_proxy_map"]):
+        idx.proxy_map = {str(k): str(v) for k, v in zip(g["proxy_keys"], g["proxy_values"])}
+    arrays = {k: g[k] for k in ("W_indptr", "W_indices", "W_data", "TF_indptr", "TF_indices", "TF_data", "tf_deg", "kin_grid", "kin_Kmat")}
+    return types.SimpleNamespace(idx=idx, **arrays)
 
 
-@pytest.mark.skipif(not __import__("pathlib").Path("/root/reference").exists(), reason="needs the reference tree (build container only)")
 @pytest.mark.parametrize("model_name,m", [("distributive", 0), ("combinatorial", 2)])
-def test_from_system_packs_the_real_reference_System(tmp_path, model_name, m):
-    """VERDICT r1: a23 was only ever tested with a SimpleNamespace.  Here the REAL global_model.network.System (imported in a child
-    process: the reference fixes MODEL at import and wants its own CWD) goes through NetworkEngine.desc_from_system, and the result must
-    equal what the reference itself packs into odeint_args (stored in the pins fixture made from the same seeded network)."""
-    import subprocess, sys
+def test_from_system_packs_the_real_reference_System(model_name, m):
+    """a23 was only ever tested with a SimpleNamespace of made-up arrays.  Here the attributes of the REAL
+    global_model.network.System (stored from a run of the reference by tools/make_golden_from_system.py: index maps, orphan -> proxy
+    redirection, CSR arrays) go through NetworkEngine.desc_from_system, and the result must equal what the reference itself packs into
+    odeint_args (stored in the pins fixture made from the same seeded network)."""
     from pathlib import Path
-    root = Path(__file__).resolve().parents[1]
-    script = tmp_path / "pack.py"; script.write_text(_REF_SCRIPT)
-    out = tmp_path / "desc.npz"
-    r = subprocess.run([sys.executable, str(script), str(root), str(out), model_name], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = np.load(out); want = np.load(root / "tests" / "golden" / f"pins_network_m{m}.npz")
+    from phoskintime_amd.global_model.engine import NetworkEngine
+    golden = Path(__file__).resolve().parents[1] / "tests" / "golden"
+    src = np.load(golden / f"from_system_m{m}.npz")
+    assert int(src["model"]) == m and bool(src["has_proxy_map"]) and src["proxy_keys"].size >= 1, model_name
+    got = NetworkEngine.desc_from_system(_reference_system(src)); want = np.load(golden / f"pins_network_m{m}.npz")
     for k in ("offset_y", "offset_s", "n_sites", "W_indptr", "W_indices", "W_data", "TF_indptr", "TF_indices", "TF_data", "tf_deg", "driver_map",
               "kin_grid", "kin_Kmat"):
         np.testing.assert_array_equal(got[k], want[k], err_msg=k)

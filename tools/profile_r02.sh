@@ -15,8 +15,8 @@ export TMPDIR=/tmp
 REPO=$PWD
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY"
 case $WHAT in
-  config3) CMD="python3 $REPO/bench.py --no-cpu-baseline --no-secondary"; CMDS="$CMD --steps 3 --warmup 1" ;;
-  network5) CMD="python3 $REPO/bench.py --only-network"; CMDS="$CMD" ;;
+  config3) CMD="python3 $REPO/bench.py --full --no-cpu-baseline --no-secondary"; CMDS="$CMD --steps 3 --warmup 1" ;;
+  network5) CMD="python3 $REPO/bench.py --full --only-network"; CMDS="$CMD" ;;
   tpr) CMD="python3 $REPO/tools/gpu_one.py 0 4 524288 20"; CMDS="python3 $REPO/tools/gpu_one.py 0 4 524288 3" ;;
   sens) CMD="python3 $REPO/tools/gpu_sens_one.py distmod 8 65536 10"; CMDS="python3 $REPO/tools/gpu_sens_one.py distmod 8 65536 2" ;;
   sens_rand) CMD="python3 $REPO/tools/gpu_sens_one.py randmod 4 16384 5"; CMDS="python3 $REPO/tools/gpu_sens_one.py randmod 4 16384 2" ;;
