@@ -104,7 +104,9 @@ enum {
 enum {
   PK_KERNEL_AUTO  = 0,  /* by batch size (default)                                                             */
   PK_KERNEL_GROUP = 1,  /* lane-group kernels (several lanes per replica) at every batch size                  */
-  PK_KERNEL_TPR   = 2   /* thread-per-replica kernels wherever one exists for (model, n_sites), else lane-group */
+  PK_KERNEL_TPR   = 2,  /* thread-per-replica kernels wherever one exists for (model, n_sites), else lane-group */
+  PK_KERNEL_WORKSPACE = 3  /* pk_network_simulate_batch only: ROS34PW2 on the HBM-workspace kernel at any network size (the kernel
+                              networks beyond one workgroup's LDS take by themselves)                                           */
 };
 
 typedef struct pk_ctx pk_ctx;
@@ -254,13 +256,21 @@ int pk_network_jacobian_batch(pk_ctx*, pk_net*, int64_t B, const double* x, int 
  * (DESIGN.md): PK_METHOD_ARK436 (order 4) where its kernel applies, else PK_METHOD_ROS34PW2 (order 3); either can be requested by name,
  * every other opts->method value means "the default"; PK_METHOD_DP5 selects the reference's explicit RK45 (jacspeedup.solve_custom,
  * jacspeedup.py:31-64; h0 = dt_init, 0 -> 0.05; max_steps <= 0 -> 2 000 000).  opts->rtol / atol / h0 / max_steps / err_norm are honoured.
- * All four topologies; combinatorial blocks (2) up to 3 sites per protein run out of registers, larger ones (<= 16 sites) in the LDS kernel. */
+ * All four topologies; combinatorial blocks (2) up to 3 sites per protein run out of registers, larger ones (<= 16 sites) in the LDS kernel.
+ * Networks beyond one workgroup's LDS (S > 1024, N > 512 or a work area over 160 KiB) integrate with ROS34PW2 in the workspace kernel:
+ * every per-candidate vector in a slab of the context's scratch arena (pk_network_workspace_bytes), no size limit but device memory;
+ * opts->kernel = PK_KERNEL_WORKSPACE selects that kernel on any network.  ARK436 and DP5 stay limited to their one-workgroup kernels. */
 int pk_network_simulate_batch(pk_ctx*, pk_net*, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                               const double* t_host, int T, const pk_solver_opts* opts, double* Y, int32_t* status, int32_t* n_steps);
 /* The integrator pk_network_simulate_batch will run for `opts` (NULL = defaults) on this network: PK_METHOD_DP5, PK_METHOD_ARK436 or
- * PK_METHOD_ROS34PW2; PK_ERR_UNSUPPORTED when ARK436 was requested and its kernel does not fit (N, sites per protein, 160 KB of LDS).  Pure
- * host arithmetic.  Host layers derive integrator-dependent defaults (tolerances) from this answer instead of re-stating the rule. */
+ * PK_METHOD_ROS34PW2 (always ROS34PW2 on networks beyond one workgroup's LDS and with opts->kernel = PK_KERNEL_WORKSPACE);
+ * PK_ERR_UNSUPPORTED when ARK436 was requested and its kernel does not fit (N, sites per protein, 160 KB of LDS), or ARK436 / DP5 together
+ * with PK_KERNEL_WORKSPACE.  Pure host arithmetic.  Host layers derive integrator-dependent defaults (tolerances) from this answer instead
+ * of re-stating the rule. */
 int pk_network_resolve_method(const pk_net*, const pk_solver_opts* opts);
+/* Bytes of the context's scratch arena the workspace kernel reserves for B candidates on this network: grid x slab, grid = min(B, workgroups
+ * resident on the context's GPU), slab = 8 (n_var + 8 S + n_K + total_sites + 6 N) bytes rounded up to 128 B -- bounded in B.  < 0 on error. */
+int64_t pk_network_workspace_bytes(pk_ctx*, const pk_net*, int64_t B);
 /* global_model.params.unpack_params (softplus of the raw decision vectors): x_raw [B,n_var] -> x_phys [B,n_var]. */
 int pk_network_unpack_batch(pk_ctx*, pk_net*, int64_t B, const double* x_raw, double* x_phys);
 

@@ -19,8 +19,8 @@ METHOD_RODAS4, METHOD_BDF2, METHOD_RK4, METHOD_LRP8, METHOD_DP5, METHOD_LRP12, M
 METHODS = {"rodas4": METHOD_RODAS4, "bdf2": METHOD_BDF2, "rk4": METHOD_RK4, "lrp8": METHOD_LRP8, "dp5": METHOD_DP5, "lrp12": METHOD_LRP12, "ark436": METHOD_ARK436, "ros34pw2": METHOD_ROS34PW2}
 LINSOLVE_AUTO, LINSOLVE_DENSE, LINSOLVE_STRUCTURED = 0, 1, 2
 LINSOLVES = {"auto": LINSOLVE_AUTO, "dense": LINSOLVE_DENSE, "structured": LINSOLVE_STRUCTURED}
-KERNEL_AUTO, KERNEL_GROUP, KERNEL_TPR = 0, 1, 2
-KERNELS = {"auto": KERNEL_AUTO, "group": KERNEL_GROUP, "tpr": KERNEL_TPR}
+KERNEL_AUTO, KERNEL_GROUP, KERNEL_TPR, KERNEL_WORKSPACE = 0, 1, 2, 3
+KERNELS = {"auto": KERNEL_AUTO, "group": KERNEL_GROUP, "tpr": KERNEL_TPR, "workspace": KERNEL_WORKSPACE}
 NORMS = {"default": 0, "max": 1, "rms": 2}
 METRICS = {"total_signal": 0, "mean_activity": 1, "variance": 2, "dynamics": 3, "l2_norm": 4}
 ST_NONFINITE, ST_MAXSTEPS, ST_HMIN = 1, 2, 4
@@ -69,6 +69,7 @@ SYMBOLS = (
     "pk_network_create", "pk_network_destroy", "pk_network_n_states", "pk_network_n_var",
     "pk_network_rhs_batch", "pk_network_jacobian_batch", "pk_network_unpack_batch", "pk_network_simulate_batch",
     "pk_network_loss_create", "pk_network_loss_destroy", "pk_network_objective_batch", "pk_network_simulate_objective_batch", "pk_network_observables_batch", "pk_frechet_batch", "pk_loss_fn_batch_host", "pk_network_resolve_method",
+    "pk_network_workspace_bytes",
     "pk_comm_unique_id", "pk_comm_init", "pk_comm_rank", "pk_comm_world", "pk_allgather_f64", "pk_comm_destroy",
 )
 
@@ -140,6 +141,7 @@ def load():
     lib.pk_network_observables_batch.restype = i32
     lib.pk_network_observables_batch.argtypes = [vp, vp, vp, i64, vp, i32, dbl, vp]
     lib.pk_network_resolve_method.restype = i32; lib.pk_network_resolve_method.argtypes = [vp, optp]
+    lib.pk_network_workspace_bytes.restype = i64; lib.pk_network_workspace_bytes.argtypes = [vp, vp, i64]
     lib.pk_loss_fn_batch_host.restype = i32
     lib.pk_loss_fn_batch_host.argtypes = [vp, i32, i32, i64, vp, i32, i32, C.POINTER(LossData), vp, i32, vp]
     lib.pk_network_unpack_batch.restype = i32; lib.pk_network_unpack_batch.argtypes = [vp, vp, i64, vp, vp]

@@ -168,6 +168,18 @@ const char* pk_last_error(pk_ctx* c) { return c ? c->err.c_str() : "null context
 int pk_ctx_device(pk_ctx* c) { return c->device; }
 void* pk_ctx_stream(pk_ctx* c) { return (void*)c->stream; }
 int pk_ctx_fail(pk_ctx* c, int code, const char* msg) { return fail(c, code, msg ? msg : ""); }
+// the scratch arena for the workspace kernels of pk_network.hip: reserve `bytes` and launch under the lock, ordered after the previous
+// scratch user whatever stream that one ran on (the pattern of the wide randmod kernels in pk_solve_protein_batch)
+int pk_ctx_scratch_launch(pk_ctx* c, size_t bytes, hipError_t (*launch)(void* scratch, hipStream_t stream, void* user), void* user) {
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  int rc = arena_reserve(c, c->scratch, bytes);
+  if (rc) return rc;
+  if (c->scratch_used) PK_HIP(c, hipStreamWaitEvent(c->stream, c->scratch_ev, 0));
+  PK_HIP(c, launch(c->scratch.p, c->stream, user));
+  PK_HIP(c, hipEventRecord(c->scratch_ev, c->stream));
+  c->scratch_used = true;
+  return PK_OK;
+}
 
 int pk_workspace_stats(pk_ctx* c, int64_t out[6]) {
   if (!c || !out) return PK_ERR_ARG;

@@ -10,7 +10,11 @@
 #include "pk_network_solve_reg.hpp"
 #include "pk_network_solve_reg2.hpp"
 #include "pk_network_rk45.hpp"
+#include "pk_network_solve_ws.hpp"
 namespace pk {
+// ROS34PW2-W with every per-candidate vector in an HBM workspace (pk_network_solve_ws.hpp, pk_inst_net_ws.hip): no size limit
+hipError_t net_ws_grid(const NetDev& n, long long B, int* grid);
+hipError_t launch_net_ws(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
@@ -27,16 +31,14 @@ struct pk_ctx;                                   // defined in pk_capi.hip
 extern "C" int pk_ctx_device(pk_ctx*);
 extern "C" void* pk_ctx_stream(pk_ctx*);
 extern "C" int pk_ctx_fail(pk_ctx*, int code, const char* msg);
+extern "C" int pk_ctx_scratch_launch(pk_ctx*, size_t bytes, hipError_t (*launch)(void* scratch, hipStream_t stream, void* user), void* user);
 
 namespace pk {
 
-// dydt[b, :] = f(t_b, y_b; x_b)
-__global__ __launch_bounds__(256) void net_rhs_kernel(const NetDev n, const double* __restrict__ x, const int x_is_raw,
-                                                      const double* __restrict__ y, const int y_batched,
-                                                      const double* __restrict__ t, const int t_batched, double* __restrict__ dydt) {
-  extern __shared__ __align__(16) double lds[];
-  const NetLds L(lds, n);
-  const long long b = blockIdx.x;
+// dydt[b, :] = f(t_b, y_b; x_b) with the work area L (LDS, or a workspace slab)
+__device__ __forceinline__ void net_rhs_one(const NetDev& n, const NetLds& L, const long long b, const double* __restrict__ x, const int x_is_raw,
+                                            const double* __restrict__ y, const int y_batched, const double* __restrict__ t, const int t_batched,
+                                            double* __restrict__ dydt) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const double* xb = x + b * n.n_var;
   for (int k = tid; k < n.n_var; k += nt) L.p[k] = x_is_raw ? softplus(xb[k]) : xb[k];
@@ -48,13 +50,17 @@ __global__ __launch_bounds__(256) void net_rhs_kernel(const NetDev n, const doub
   for (int k = tid; k < n.S; k += nt) dydt[b * n.S + k] = net_state_rhs(n, L, k);
 }
 
-// J[b, r, c] = d f_r / d y_c, row-major, analytic
-__global__ __launch_bounds__(256) void net_jac_kernel(const NetDev n, const double* __restrict__ x, const int x_is_raw,
+__global__ __launch_bounds__(256) void net_rhs_kernel(const NetDev n, const double* __restrict__ x, const int x_is_raw,
                                                       const double* __restrict__ y, const int y_batched,
-                                                      const double* __restrict__ t, const int t_batched, double* __restrict__ J) {
+                                                      const double* __restrict__ t, const int t_batched, double* __restrict__ dydt) {
   extern __shared__ __align__(16) double lds[];
-  const NetLds L(lds, n);
-  const long long b = blockIdx.x;
+  net_rhs_one(n, NetLds(lds, n), blockIdx.x, x, x_is_raw, y, y_batched, t, t_batched, dydt);
+}
+
+// J[b, r, c] = d f_r / d y_c, row-major, analytic
+__device__ __forceinline__ void net_jac_one(const NetDev& n, const NetLds& L, const long long b, const double* __restrict__ x, const int x_is_raw,
+                                            const double* __restrict__ y, const int y_batched, const double* __restrict__ t, const int t_batched,
+                                            double* __restrict__ J) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const double* xb = x + b * n.n_var;
   for (int k = tid; k < n.n_var; k += nt) L.p[k] = x_is_raw ? softplus(xb[k]) : xb[k];
@@ -83,6 +89,29 @@ __global__ __launch_bounds__(256) void net_jac_kernel(const NetDev n, const doub
         for (int m = 0; m < cj; ++m) row[sj + 1 + m] += w;
       }
     }
+  }
+}
+
+__global__ __launch_bounds__(256) void net_jac_kernel(const NetDev n, const double* __restrict__ x, const int x_is_raw,
+                                                      const double* __restrict__ y, const int y_batched,
+                                                      const double* __restrict__ t, const int t_batched, double* __restrict__ J) {
+  extern __shared__ __align__(16) double lds[];
+  net_jac_one(n, NetLds(lds, n), blockIdx.x, x, x_is_raw, y, y_batched, t, t_batched, J);
+}
+
+// networks whose work area exceeds 160 KiB of LDS: the same bodies on a workspace slab per workgroup, persistent over the batch
+__host__ __device__ inline size_t net_rhs_ws_slab_doubles(const NetDev& n) {
+  return ((size_t)n.n_var + n.S + n.n_K + n.sites + 3 * (size_t)n.N + 15) / 16 * 16;
+}
+template <bool JAC>
+__global__ __launch_bounds__(256) void net_rhs_ws_kernel(const NetDev n, const long long B, double* __restrict__ ws, const size_t slab,
+                                                         const double* __restrict__ x, const int x_is_raw, const double* __restrict__ y,
+                                                         const int y_batched, const double* __restrict__ t, const int t_batched, double* __restrict__ out) {
+  const NetLds L(ws + (size_t)blockIdx.x * slab, n);
+  for (long long b = blockIdx.x; b < B; b += gridDim.x) {
+    __syncthreads();                                   // the previous candidate of this workgroup is done with the slab
+    if (JAC) net_jac_one(n, L, b, x, x_is_raw, y, y_batched, t, t_batched, out);
+    else     net_rhs_one(n, L, b, x, x_is_raw, y, y_batched, t, t_batched, out);
   }
 }
 
@@ -178,12 +207,13 @@ pk_net* pk_network_create(pk_ctx* c, const pk_network_desc* d) {
     v.n_lanes = (int)lanes.size();
     v.lane_unit = upload(n, lanes.data(), lanes.size(), ok);
   }
-  if (!ok || n->lds_bytes > 160 * 1024) {
-    pk_ctx_fail(c, ok ? PK_ERR_UNSUPPORTED : PK_ERR_NOMEM, ok ? "network too large for one workgroup's LDS (160 KiB)" : "hipMalloc / hipMemcpy failed");
+  if (!ok) {
+    pk_ctx_fail(c, PK_ERR_NOMEM, "hipMalloc / hipMemcpy failed");
     pk_network_destroy(n);
     return nullptr;
   }
-  if (n->lds_bytes > 48 * 1024) {
+  // beyond 160 KiB the RHS / Jacobian run on workspace slabs instead of dynamic LDS (net_rhs_ws_kernel)
+  if (n->lds_bytes > 48 * 1024 && n->lds_bytes <= 160 * 1024) {
     (void)hipFuncSetAttribute((const void*)pk::net_rhs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n->lds_bytes);
     (void)hipFuncSetAttribute((const void*)pk::net_jac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n->lds_bytes);
   }
@@ -216,11 +246,39 @@ static int net_args_ok(pk_ctx* c, pk_net* n, int64_t B, const void* x, const voi
   return PK_OK;
 }
 
+// RHS / Jacobian of a network whose work area exceeds 160 KiB: a persistent grid of min(B, resident workgroups) on slabs of the context's
+// scratch arena
+struct NetRhsWsLaunch {
+  const pk::NetDev* d; long long B; int grid; bool jac;
+  const double *x, *y, *t; int x_is_raw, y_batched, t_batched; double* out;
+};
+static hipError_t net_rhs_ws_launch(void* scratch, hipStream_t st, void* user) {
+  const NetRhsWsLaunch& q = *(const NetRhsWsLaunch*)user;
+  const size_t slab = pk::net_rhs_ws_slab_doubles(*q.d);
+  if (q.jac) hipLaunchKernelGGL(pk::net_rhs_ws_kernel<true>, dim3((unsigned)q.grid), dim3(256), 0, st, *q.d, q.B, (double*)scratch, slab, q.x,
+                                q.x_is_raw, q.y, q.y_batched, q.t, q.t_batched, q.out);
+  else       hipLaunchKernelGGL(pk::net_rhs_ws_kernel<false>, dim3((unsigned)q.grid), dim3(256), 0, st, *q.d, q.B, (double*)scratch, slab, q.x,
+                                q.x_is_raw, q.y, q.y_batched, q.t, q.t_batched, q.out);
+  return hipGetLastError();
+}
+static int net_rhs_ws(pk_ctx* c, pk_net* n, bool jac, int64_t B, const double* x, int x_is_raw, const double* y, int y_is_batched,
+                      const double* t, int t_is_batched, double* out) {
+  int dev = pk_ctx_device(c), cus = 0, per_cu = 0;
+  const void* k = jac ? (const void*)pk::net_rhs_ws_kernel<true> : (const void*)pk::net_rhs_ws_kernel<false>;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0) != hipSuccess)
+    return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+  NetRhsWsLaunch q{&n->d, (long long)B, (int)std::min<long long>(B, (long long)std::max(per_cu, 1) * std::max(cus, 1)), jac,
+                   x, y, t, x_is_raw, y_is_batched ? 1 : 0, t_is_batched ? 1 : 0, out};
+  return pk_ctx_scratch_launch(c, (size_t)q.grid * pk::net_rhs_ws_slab_doubles(n->d) * sizeof(double), net_rhs_ws_launch, &q);
+}
+
 int pk_network_rhs_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y, int y_is_batched,
                          const double* t, int t_is_batched, double* dydt) {
   int rc = net_args_ok(c, n, B, x, y, t, dydt);
   if (rc || B == 0) return rc;
   if (hipSetDevice(pk_ctx_device(c)) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipSetDevice");
+  if (n->lds_bytes > 160 * 1024) return net_rhs_ws(c, n, false, B, x, x_is_raw, y, y_is_batched, t, t_is_batched, dydt);
   hipLaunchKernelGGL(pk::net_rhs_kernel, dim3((unsigned)B), dim3(256), n->lds_bytes, (hipStream_t)pk_ctx_stream(c), n->d, x, x_is_raw, y,
                      y_is_batched, t, t_is_batched, dydt);
   hipError_t e = hipGetLastError();
@@ -232,19 +290,30 @@ int pk_network_jacobian_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, 
   int rc = net_args_ok(c, n, B, x, y, t, J);
   if (rc || B == 0) return rc;
   if (hipSetDevice(pk_ctx_device(c)) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipSetDevice");
+  if (n->lds_bytes > 160 * 1024) return net_rhs_ws(c, n, true, B, x, x_is_raw, y, y_is_batched, t, t_is_batched, J);
   hipLaunchKernelGGL(pk::net_jac_kernel, dim3((unsigned)B), dim3(256), n->lds_bytes, (hipStream_t)pk_ctx_stream(c), n->d, x, x_is_raw, y,
                      y_is_batched, t, t_is_batched, J);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(e));
 }
 
+// Networks beyond the one-workgroup LDS kernels (S > 1024, N > 512, or more than 160 KiB of LDS for the general one): they integrate with
+// ROS34PW2 in the workspace kernel (pk_network_solve_ws.hpp).  Small combinatorial blocks run out of registers and are exempt from the LDS rule.
+static bool net_needs_ws(const pk_net* n) {
+  const bool comb_reg = n->d.model == 2 && n->max_sites <= 3 && n->d.N <= 256;
+  return n->d.S > 1024 || n->d.N > 512 || (!comb_reg && n->solve_lds_bytes > 160 * 1024);
+}
+
 // Which integrator pk_network_simulate_batch runs for these options on this network -- the single source of truth (the Python host layer
 // picks its default tolerances from it).  PK_METHOD_DP5 on request; PK_METHOD_ARK436 where its kernel fits and is the default (or was
-// asked for); otherwise PK_METHOD_ROS34PW2.  PK_ERR_UNSUPPORTED when ARK436 was requested and cannot run.
+// asked for); otherwise PK_METHOD_ROS34PW2 (always on the workspace kernel: networks beyond the LDS kernels, or opts->kernel =
+// PK_KERNEL_WORKSPACE).  PK_ERR_UNSUPPORTED when ARK436 was requested and cannot run, or DP5 / ARK436 together with PK_KERNEL_WORKSPACE.
 int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) {
   if (!n) return PK_ERR_ARG;
   const int method = opts ? opts->method : PK_METHOD_LRP12, linsolve = opts ? opts->linsolve : PK_LINSOLVE_AUTO;
+  if (opts && opts->kernel == PK_KERNEL_WORKSPACE) return (method == PK_METHOD_DP5 || method == PK_METHOD_ARK436) ? PK_ERR_UNSUPPORTED : PK_METHOD_ROS34PW2;
   if (method == PK_METHOD_DP5) return PK_METHOD_DP5;
+  if (net_needs_ws(n)) return method == PK_METHOD_ARK436 ? PK_ERR_UNSUPPORTED : PK_METHOD_ROS34PW2;
   const int threads_a = ((n->d.N + 63) / 64) * 64;
   const bool ark_fits = n->d.N <= 256 && n->max_sites <= (n->d.model == 2 ? 3 : 8) && linsolve != PK_LINSOLVE_STRUCTURED;
   // one thread per protein (N <= 256), or [r3] the dense lane layout of topologies 0 / 1 / 4 (<= 512 lanes: up to 512 proteins)
@@ -271,8 +340,10 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   // combinatorial blocks: <= 3 sites per protein (and N <= 256) run one thread per protein out of registers (pk_network_solve_reg2.hpp);
   // larger blocks run in the general LDS kernel with the same approximate factorisation, swept serially by the protein's thread
   const bool comb_reg = n->d.model == 2 && n->max_sites <= 3 && n->d.N <= 256;
-  if (!dp5 && !(n->d.model == 2 && comb_reg) && n->solve_lds_bytes > 160 * 1024) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network too large for one workgroup's LDS (160 KiB)");
-  if (n->d.S > 1024 || n->d.N > 512) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "simulate: S <= 1024 states and N <= 512 proteins per network");
+  // networks beyond the one-workgroup LDS kernels -- and any network on request (opts->kernel = PK_KERNEL_WORKSPACE) -- take the workspace kernel
+  const bool ws = !dp5 && (net_needs_ws(n) || (opts_in && opts_in->kernel == PK_KERNEL_WORKSPACE));
+  if (dp5 && opts_in->kernel == PK_KERNEL_WORKSPACE) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_KERNEL_WORKSPACE integrates with PK_METHOD_ROS34PW2 only");
+  if (dp5 && (n->d.S > 1024 || n->d.N > 512)) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_METHOD_DP5: S <= 1024 states and N <= 512 proteins per network");
   for (int k = 1; k < T; ++k) if (!(t_host[k] > t_host[k - 1])) return pk_ctx_fail(c, PK_ERR_ARG, "t must be strictly increasing");
   pk_solver_opts o;
   if (opts_in) o = *opts_in; else pk_default_opts(&o);
@@ -332,6 +403,19 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
         hipMemcpy(n->stop_out_dev, so.data(), so.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
       return pk_ctx_fail(c, PK_ERR_HIP, "hipMemcpy");
     a.stops_p = n->stops_dev; a.stop_out_p = n->stop_out_dev;
+  }
+  if (ws) {
+    // ROS34PW2 on workspace slabs (pk_network_solve_ws.hpp): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
+    if (fused) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: not on the workspace kernel; use pk_network_simulate_batch + pk_network_objective_batch");
+    if (o.method == PK_METHOD_ARK436)
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: not on the workspace kernel (networks beyond one workgroup's LDS); use PK_METHOD_ROS34PW2");
+    struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; } q{&n->d, &a, (long long)B, 0};
+    if (pk::net_ws_grid(n->d, (long long)B, &q.grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+    auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
+      const Q& r = *(const Q*)user;
+      return pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
+    };
+    return pk_ctx_scratch_launch(c, (size_t)q.grid * pk::net_ws_slab_doubles(n->d) * sizeof(double), launch, &q);
   }
   if (dp5) {
     const size_t lb = pk::net_rk45_lds_bytes(n->d);
@@ -409,6 +493,15 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(e));
+}
+
+int64_t pk_network_workspace_bytes(pk_ctx* c, const pk_net* n, int64_t B) {
+  if (!c || !n) return PK_ERR_ARG;
+  if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
+  if (hipSetDevice(pk_ctx_device(c)) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipSetDevice");
+  int grid = 0;
+  if (pk::net_ws_grid(n->d, (long long)B, &grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+  return (int64_t)grid * (int64_t)(pk::net_ws_slab_doubles(n->d) * sizeof(double));
 }
 
 int pk_network_simulate_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,

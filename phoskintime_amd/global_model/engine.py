@@ -147,13 +147,17 @@ class NetworkEngine:
         Returns (Y, status [B], n_steps [B, 2]) as GPU tensors; flagged candidates have NaN rows (callers test np.isfinite,
         optproblem.py:125-133).  method = "auto": the order-4 additive method ARK436 where its kernel applies (topologies 0 / 1 / 4, <= 8
         sites per protein, N <= 256), else the order-3 Rosenbrock-W method; "ark" / "rosw" request one of them; "dp5": the reference's
-        explicit RK45 (solvers.py:293-758) step for step.  err_norm = "max" (default: every component inside its tolerance) or "rms" (ODEPACK's weighted
+        explicit RK45 (solvers.py:293-758) step for step.  Networks of any size run: those beyond one workgroup's LDS integrate with the
+        order-3 method on the HBM-workspace kernel.  kernel = "auto" (the library's choice), "lds" (the general LDS kernel where it fits)
+        or "workspace" (the HBM-workspace kernel at any size, order-3 method only).  err_norm = "max" (default: every component inside its tolerance) or "rms" (ODEPACK's weighted
         root-mean-square norm, i.e. what the reference's LSODA controls with the same rtol / atol: 1.4-1.7x fewer steps).  Measured
         (tools/gpu_norm_scan.py): on the reference-run fixtures the RMS run at 1e-8 / 1e-8 lands 0.04-0.27 band widths from LSODA at 1e-12
         (the reference's own LSODA run at those settings: 0.05-0.43), but on random full-size combinatorial populations it reaches 2 band
         widths and at 1e-5 / 1e-7 it is 6x less accurate than LSODA -- the order-3 method's error constant is larger.  Hence opt-in."""
         if method not in ("auto", "ark", "rosw", "dp5"):
             raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
+        if kernel not in ("auto", "lds", "workspace"):
+            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
         if rtol is None or atol is None:
             # parity-grade defaults (worst band error over every reference-run fixture <= 0.3, tools/gpu_norm_scan.py): the order-4 method
             # at the reference optimiser's own tolerances (config.toml:403-404), the order-3 method at 1e-7 / 1e-9.  Which of the two
@@ -180,9 +184,8 @@ class NetworkEngine:
         Y = torch.empty((B, T, self.S), dtype=torch.float64, device=dev)
         status = torch.zeros((B,), dtype=torch.int32, device=dev)
         nsteps = torch.zeros((B, 2), dtype=torch.int32, device=dev)
-        # kernel = "auto": register-resident one-thread-per-protein kernel when eligible; "lds": the general LDS kernel
-        opts = _capi.default_opts(rtol=rtol, atol=atol, max_steps=max_steps, h0=h0, linsolve=("structured" if kernel == "lds" else "auto"),
-                                  method={"dp5": "dp5", "ark": "ark436", "rosw": "ros34pw2"}.get(method), err_norm=err_norm)
+        # kernel = "auto": register-resident one-thread-per-protein kernel when eligible; "lds": the general LDS kernel; "workspace": HBM slabs
+        opts = self._opts(method, kernel, rtol=rtol, atol=atol, max_steps=max_steps, h0=h0, err_norm=err_norm)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         self.ctx.check(self.ctx.lib.pk_network_simulate_batch(self.ctx.handle, self._h, B, _ptr(xd), int(raw), _ptr(yd), yb, th.ctypes.data, T,
                                                              C.byref(opts), _ptr(Y), _ptr(status), _ptr(nsteps)))
@@ -234,11 +237,25 @@ class NetworkEngine:
         """The integrator ``simulate_batch(method=, kernel=)`` will run on this network -- "ark", "rosw" or "dp5" -- as decided by the
         library itself (``pk_network_resolve_method``: network size, sites per protein AND the LDS footprint of the order-4 kernel).
         Raises PhoskinError when "ark" was requested and cannot run."""
-        opts = _capi.default_opts(linsolve=("structured" if kernel == "lds" else "auto"), method={"dp5": "dp5", "ark": "ark436", "rosw": "ros34pw2"}.get(method))
-        m = _capi.load().pk_network_resolve_method(self._h, C.byref(opts))
+        m = _capi.load().pk_network_resolve_method(self._h, C.byref(self._opts(method, kernel)))
         if m < 0:
+            if kernel == "workspace":
+                raise _capi.PhoskinError(f"method={method!r}: the workspace kernel integrates with the order-3 method ('rosw') only")
             raise _capi.PhoskinError("method='ark': the order-4 kernel does not fit this network (N <= 256, <= 8 sites per protein, 160 KB of LDS)")
         return {_capi.METHOD_DP5: "dp5", _capi.METHOD_ARK436: "ark"}.get(m, "rosw")
+
+    @staticmethod
+    def _opts(method: str, kernel: str, **kw):
+        return _capi.default_opts(linsolve=("structured" if kernel == "lds" else "auto"), kernel=("workspace" if kernel == "workspace" else "auto"),
+                                  method={"dp5": "dp5", "ark": "ark436", "rosw": "ros34pw2"}.get(method), **kw)
+
+    def workspace_bytes(self, B: int) -> int:
+        """HBM the workspace kernel takes from the context's scratch arena for B candidates (``pk_network_workspace_bytes``):
+        min(B, resident workgroups) slabs of 8 (n_var + 8 S + n_K + total_sites + 6 N) bytes, each rounded up to 128 B."""
+        v = int(self.ctx.lib.pk_network_workspace_bytes(self.ctx.handle, self._h, int(B)))
+        if v < 0:
+            self.ctx.check(v)
+        return v
 
     def ark_eligible(self) -> bool:
         """Whether pk_network_simulate_batch runs the order-4 additive integrator on this network BY DEFAULT."""

@@ -61,3 +61,80 @@ def random_candidates(net: dict, B: int, seed: int = 0, spread: float = 0.5) -> 
     rng = np.random.default_rng(seed)
     base = default_candidate(net)
     return base[None, :] * np.exp(spread * rng.standard_normal((B, base.size)))
+
+
+_SCALARS = ("N", "n_K", "total_sites", "S", "n_W_rows")
+
+
+def tile_network(desc: dict, K: int) -> dict:
+    """The disjoint union of K copies of a network description (``make_network`` output or a golden file's topology): copy c's states,
+    sites, proteins and kinases follow those of copies 0 .. c-1.  Kinase indices (``W_indices``, ``driver_map`` where >= 0) move by
+    c n_K, TF indices by c N, ``kin_Kmat`` is stacked and ``kin_grid`` shared, so copy c integrates exactly like the single network.
+    Scalar sizes present in ``desc`` (N, n_K, total_sites, S, n_W_rows) are scaled; ``n_states`` (combinatorial fixtures) is tiled."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    oy, os_, ns = (np.asarray(desc[k]) for k in ("offset_y", "offset_s", "n_sites"))
+    N = oy.size
+    n_K = np.asarray(desc["kin_Kmat"]).shape[0]
+    model = int(desc["model"])
+    blk = (1 + (1 << ns.astype(np.int64))) if model == 2 else (2 + ns.astype(np.int64))
+    S, sites = int(blk.sum()), int(ns.sum())
+    wp, tp = np.asarray(desc["W_indptr"]), np.asarray(desc["TF_indptr"])
+    nnzW, nnzT = int(wp[-1]), int(tp[-1])
+    drv = np.asarray(desc["driver_map"])
+    cs = range(K)
+    out = {k: v for k, v in desc.items() if k in _SCALARS or k in ("model", "kin_grid")}
+    out.update(
+        offset_y=np.concatenate([oy + c * S for c in cs]).astype(np.int32),
+        offset_s=np.concatenate([os_ + c * sites for c in cs]).astype(np.int32),
+        n_sites=np.tile(ns, K).astype(np.int32),
+        W_indptr=np.concatenate([wp[:1]] + [wp[1:] + c * nnzW for c in cs]).astype(np.int32),
+        W_indices=np.concatenate([np.asarray(desc["W_indices"])[:nnzW] + c * n_K for c in cs]).astype(np.int32),
+        W_data=np.tile(np.asarray(desc["W_data"], dtype=np.float64)[:nnzW], K),
+        TF_indptr=np.concatenate([tp[:1]] + [tp[1:] + c * nnzT for c in cs]).astype(np.int32),
+        TF_indices=np.concatenate([np.asarray(desc["TF_indices"])[:nnzT] + c * N for c in cs]).astype(np.int32),
+        TF_data=np.tile(np.asarray(desc["TF_data"], dtype=np.float64)[:nnzT], K),
+        tf_deg=np.tile(np.asarray(desc["tf_deg"], dtype=np.float64), K),
+        driver_map=np.concatenate([np.where(drv >= 0, drv + c * n_K, drv) for c in cs]).astype(np.int32),
+        kin_grid=np.asarray(desc["kin_grid"], dtype=np.float64),
+        kin_Kmat=np.concatenate([np.asarray(desc["kin_Kmat"], dtype=np.float64)] * K, axis=0),
+    )
+    for k in _SCALARS:
+        if k in desc:
+            out[k] = np.asarray(int(np.asarray(desc[k])) * K)
+    if "n_states" in desc:
+        out["n_states"] = np.tile(np.asarray(desc["n_states"]), K)
+    return out
+
+
+def _blocks(x: np.ndarray, n_K: int, N: int, sites: int):
+    """[c_k | A | B | C | D | Dp | E] blocks and tf_scale of candidate rows x [..., n_var]."""
+    cuts = np.cumsum([n_K, N, N, N, N, sites, N])
+    return np.split(x[..., :-1], cuts[:-1], axis=-1), x[..., -1]
+
+
+def _dims(desc: dict):
+    return np.asarray(desc["kin_Kmat"]).shape[0], np.asarray(desc["offset_y"]).size, int(np.asarray(desc["n_sites"]).sum())
+
+
+def union_candidate(rows, desc: dict) -> np.ndarray:
+    """One candidate of the K-copy union of network ``desc`` from K candidates of the single network (rows [K, n_var], or
+    [B, K, n_var] -> [B, n_var of the union]): each parameter block is concatenated copy by copy; the union has ONE tf_scale, so every
+    row must carry the same one."""
+    n_K, N, sites = _dims(desc)
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.shape[-1] != n_K + 5 * N + sites + 1:
+        raise ValueError("rows must be [..., K, n_var] of the single network")
+    parts, ts = _blocks(rows, n_K, N, sites)
+    if not np.all(ts == ts[..., :1]):
+        raise ValueError("the copies of a union share one tf_scale")
+    flat = lambda a: a.reshape(a.shape[:-2] + (-1,))
+    return np.concatenate([flat(p) for p in parts] + [ts[..., :1]], axis=-1)
+
+
+def tile_candidate(x, K: int, desc: dict) -> np.ndarray:
+    """Candidate(s) x ([n_var] or [B, n_var]) of network ``desc`` -> the same candidate(s) on ``tile_network(desc, K)``: every copy
+    gets x's parameters, the one global tf_scale is kept."""
+    x = np.asarray(x, dtype=np.float64)
+    return union_candidate(np.repeat(x[..., None, :], int(K), axis=-2), desc)
