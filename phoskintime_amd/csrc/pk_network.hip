@@ -10,9 +10,10 @@
 #include "pk_network_solve_reg.hpp"
 #include "pk_network_solve_reg2.hpp"
 #include "pk_network_rk45.hpp"
-#include "pk_network_solve_ws.hpp"
 namespace pk {
-// ROS34PW2-W with every per-candidate vector in an HBM workspace (pk_network_solve_ws.hpp, pk_inst_net_ws.hip): no size limit
+// persistent grid: min(B, workgroups of `kernel` at `threads` each resident on the current device at once)
+hipError_t net_persistent_grid(const void* kernel, int threads, long long B, int* grid);
+// ROS34PW2-W with every per-candidate vector in an HBM workspace (net_solve_ws_kernel, pk_inst_net_ws.hip): no size limit
 hipError_t net_ws_grid(const NetDev& n, long long B, int* grid);
 hipError_t launch_net_ws(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
@@ -263,13 +264,9 @@ static hipError_t net_rhs_ws_launch(void* scratch, hipStream_t st, void* user) {
 }
 static int net_rhs_ws(pk_ctx* c, pk_net* n, bool jac, int64_t B, const double* x, int x_is_raw, const double* y, int y_is_batched,
                       const double* t, int t_is_batched, double* out) {
-  int dev = pk_ctx_device(c), cus = 0, per_cu = 0;
+  NetRhsWsLaunch q{&n->d, (long long)B, 0, jac, x, y, t, x_is_raw, y_is_batched ? 1 : 0, t_is_batched ? 1 : 0, out};
   const void* k = jac ? (const void*)pk::net_rhs_ws_kernel<true> : (const void*)pk::net_rhs_ws_kernel<false>;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0) != hipSuccess)
-    return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
-  NetRhsWsLaunch q{&n->d, (long long)B, (int)std::min<long long>(B, (long long)std::max(per_cu, 1) * std::max(cus, 1)), jac,
-                   x, y, t, x_is_raw, y_is_batched ? 1 : 0, t_is_batched ? 1 : 0, out};
+  if (pk::net_persistent_grid(k, 256, (long long)B, &q.grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
   return pk_ctx_scratch_launch(c, (size_t)q.grid * pk::net_rhs_ws_slab_doubles(n->d) * sizeof(double), net_rhs_ws_launch, &q);
 }
 
@@ -297,33 +294,62 @@ int pk_network_jacobian_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, 
   return e == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(e));
 }
 
-// Networks beyond the one-workgroup LDS kernels (S > 1024, N > 512, or more than 160 KiB of LDS for the general one): they integrate with
-// ROS34PW2 in the workspace kernel (pk_network_solve_ws.hpp).  Small combinatorial blocks run out of registers and are exempt from the LDS rule.
-static bool net_needs_ws(const pk_net* n) {
-  const bool comb_reg = n->d.model == 2 && n->max_sites <= 3 && n->d.N <= 256;
-  return n->d.S > 1024 || n->d.N > 512 || (!comb_reg && n->solve_lds_bytes > 160 * 1024);
-}
+// Which kernel pk_network_simulate_batch runs for these options on this network, and with which method: the single source of truth (the
+// Python host layer picks its default tolerances from the method).  PK_METHOD_DP5 on request; PK_METHOD_ARK436 where its kernel fits and
+// is the default (or was asked for); otherwise PK_METHOD_ROS34PW2.  ROS34PW2 always runs on the workspace kernel for networks beyond the
+// one-workgroup LDS kernels (S > 1024, N > 512, or more than 160 KiB of LDS for the general one; small combinatorial blocks run out of
+// registers and are exempt) and on request (opts->kernel = PK_KERNEL_WORKSPACE).  A refused plan has code PK_ERR_UNSUPPORTED and a
+// message; its method is then PK_ERR_UNSUPPORTED, except for a DP5 request on a network too large for the DP5 kernel.
+enum class NetKernel { DP5, Workspace, ArkPair, Ark, CombReg, Reg, Lds };
+struct NetPlan {
+  int method;
+  NetKernel kernel;
+  int code;
+  const char* refusal;
+  int threads;                                   // ARK and register kernels: one thread per protein, in whole waves
+};
 
-// Which integrator pk_network_simulate_batch runs for these options on this network -- the single source of truth (the Python host layer
-// picks its default tolerances from it).  PK_METHOD_DP5 on request; PK_METHOD_ARK436 where its kernel fits and is the default (or was
-// asked for); otherwise PK_METHOD_ROS34PW2 (always on the workspace kernel: networks beyond the LDS kernels, or opts->kernel =
-// PK_KERNEL_WORKSPACE).  PK_ERR_UNSUPPORTED when ARK436 was requested and cannot run, or DP5 / ARK436 together with PK_KERNEL_WORKSPACE.
-int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) {
-  if (!n) return PK_ERR_ARG;
-  const int method = opts ? opts->method : PK_METHOD_LRP12, linsolve = opts ? opts->linsolve : PK_LINSOLVE_AUTO;
-  if (opts && opts->kernel == PK_KERNEL_WORKSPACE) return (method == PK_METHOD_DP5 || method == PK_METHOD_ARK436) ? PK_ERR_UNSUPPORTED : PK_METHOD_ROS34PW2;
-  if (method == PK_METHOD_DP5) return PK_METHOD_DP5;
-  if (net_needs_ws(n)) return method == PK_METHOD_ARK436 ? PK_ERR_UNSUPPORTED : PK_METHOD_ROS34PW2;
-  const int threads_a = ((n->d.N + 63) / 64) * 64;
-  const bool ark_fits = n->d.N <= 256 && n->max_sites <= (n->d.model == 2 ? 3 : 8) && linsolve != PK_LINSOLVE_STRUCTURED;
+static NetPlan net_plan(const pk_net* n, const pk_solver_opts* opts) {
+  const pk::NetDev& d = n->d;
+  const int method = opts ? opts->method : PK_METHOD_LRP12;
+  const bool structured = opts && opts->linsolve == PK_LINSOLVE_STRUCTURED;
+  const bool ws_forced = opts && opts->kernel == PK_KERNEL_WORKSPACE;
+  const int threads = ((d.N + 63) / 64) * 64;
+  auto take = [&](int m, NetKernel k) { return NetPlan{m, k, PK_OK, nullptr, threads}; };
+  auto refuse = [&](int m, const char* why) { return NetPlan{m, NetKernel::Lds, PK_ERR_UNSUPPORTED, why, threads}; };
+  if (method == PK_METHOD_DP5) {
+    if (ws_forced) return refuse(PK_ERR_UNSUPPORTED, "PK_KERNEL_WORKSPACE integrates with PK_METHOD_ROS34PW2 only");
+    if (d.S > 1024 || d.N > 512) return refuse(PK_METHOD_DP5, "PK_METHOD_DP5: S <= 1024 states and N <= 512 proteins per network");
+    if (pk::net_rk45_lds_bytes(d) > 160 * 1024) return refuse(PK_METHOD_DP5, "network too large for one workgroup's LDS (160 KiB)");
+    return take(PK_METHOD_DP5, NetKernel::DP5);
+  }
+  // combinatorial blocks: <= 3 sites per protein (and N <= 256) run one thread per protein out of registers (pk_network_solve_reg2.hpp);
+  // larger blocks run in the general LDS kernel with the same approximate factorisation, swept serially by the protein's thread
+  const bool comb_reg = d.model == 2 && n->max_sites <= 3 && d.N <= 256;
+  if (ws_forced || d.S > 1024 || d.N > 512 || (!comb_reg && n->solve_lds_bytes > 160 * 1024)) {
+    if (method == PK_METHOD_ARK436)
+      return refuse(PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: not on the workspace kernel (networks beyond one workgroup's LDS); use PK_METHOD_ROS34PW2");
+    return take(PK_METHOD_ROS34PW2, NetKernel::Workspace);
+  }
   // one thread per protein (N <= 256), or [r3] the dense lane layout of topologies 0 / 1 / 4 (<= 512 lanes: up to 512 proteins)
-  const bool ark_ok = (ark_fits && pk::net_ark_lds_bytes(n->d, n->nnzT, n->max_sites, threads_a) <= 160 * 1024) ||
-                      (linsolve != PK_LINSOLVE_STRUCTURED && pk::net_arkp_fits(n->d, n->max_sites));
-  if (method == PK_METHOD_ARK436) return ark_ok ? PK_METHOD_ARK436 : PK_ERR_UNSUPPORTED;
+  const bool ark_fits = d.N <= 256 && n->max_sites <= (d.model == 2 ? 3 : 8) && !structured;
+  const bool pair = pk::net_arkp_fits(d, n->max_sites);
+  const bool ark_ok = (ark_fits && pk::net_ark_lds_bytes(d, n->nnzT, n->max_sites, threads) <= 160 * 1024) || (!structured && pair);
+  if (method == PK_METHOD_ARK436 && !ark_ok)
+    return refuse(PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: <= 8 sites per protein and N <= 256 (topologies 0 / 1 / 4: <= 512 lanes of the dense layout); "
+                                      "combinatorial topology: <= 3 sites, N <= 256; use PK_METHOD_ROS34PW2");
   // [r3] the combinatorial topology takes the additive method by default too: with the EXACT block solve (parity elimination of the
   // bit-pattern block, pk_network_solve_ark.hpp) it needs 4.6x fewer steps than the order-3 method and runs 1.8x faster at equal band error
-  return (ark_ok && method != PK_METHOD_ROS34PW2) ? PK_METHOD_ARK436 : PK_METHOD_ROS34PW2;
+  if (ark_ok && method != PK_METHOD_ROS34PW2) return take(PK_METHOD_ARK436, pair ? NetKernel::ArkPair : NetKernel::Ark);
+  // ROS34PW2: the register-resident kernels (one thread per protein) when every block fits their per-thread arrays; opts->linsolve ==
+  // PK_LINSOLVE_STRUCTURED forces the LDS kernel (kept as the general fallback and as the A/B reference)
+  if (comb_reg && !structured) return take(PK_METHOD_ROS34PW2, NetKernel::CombReg);
+  if (d.model != 2 && d.N <= 256 && n->max_sites <= 8 && n->solve_reg_lds_bytes <= 64 * 1024 && !structured)
+    return take(PK_METHOD_ROS34PW2, NetKernel::Reg);
+  return take(PK_METHOD_ROS34PW2, NetKernel::Lds);
 }
+
+int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { return n ? net_plan(n, opts).method : PK_ERR_ARG; }
 
 // `fused`: null, or the loss fields of NetSolveArgs filled in (pk_network_simulate_objective_batch); Y may then be null
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
@@ -335,21 +361,15 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   if (B == 0) return PK_OK;
   if (!x || !y0 || (!Y && !fused)) return pk_ctx_fail(c, PK_ERR_ARG, "null pointer");
   if (B > 0x7fffffffLL) return pk_ctx_fail(c, PK_ERR_ARG, "batch too large for one launch");
-  const bool dp5 = opts_in && opts_in->method == PK_METHOD_DP5;
   if (n->d.model == 2 && n->max_sites > 16) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "combinatorial topology: <= 16 sites per protein");
-  // combinatorial blocks: <= 3 sites per protein (and N <= 256) run one thread per protein out of registers (pk_network_solve_reg2.hpp);
-  // larger blocks run in the general LDS kernel with the same approximate factorisation, swept serially by the protein's thread
-  const bool comb_reg = n->d.model == 2 && n->max_sites <= 3 && n->d.N <= 256;
-  // networks beyond the one-workgroup LDS kernels -- and any network on request (opts->kernel = PK_KERNEL_WORKSPACE) -- take the workspace kernel
-  const bool ws = !dp5 && (net_needs_ws(n) || (opts_in && opts_in->kernel == PK_KERNEL_WORKSPACE));
-  if (dp5 && opts_in->kernel == PK_KERNEL_WORKSPACE) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_KERNEL_WORKSPACE integrates with PK_METHOD_ROS34PW2 only");
-  if (dp5 && (n->d.S > 1024 || n->d.N > 512)) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_METHOD_DP5: S <= 1024 states and N <= 512 proteins per network");
+  const NetPlan plan = net_plan(n, opts_in);
+  if (plan.code != PK_OK) return pk_ctx_fail(c, plan.code, plan.refusal);
+  const bool dp5 = plan.kernel == NetKernel::DP5;
   for (int k = 1; k < T; ++k) if (!(t_host[k] > t_host[k - 1])) return pk_ctx_fail(c, PK_ERR_ARG, "t must be strictly increasing");
   pk_solver_opts o;
   if (opts_in) o = *opts_in; else pk_default_opts(&o);
   if (!(o.rtol > 0.0 && o.atol >= 0.0)) return pk_ctx_fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
   if (o.max_steps <= 0) o.max_steps = dp5 ? 2000000 : 1000000;      // solvers.py:294 max_steps = 2_000_000
-  if (dp5 && pk::net_rk45_lds_bytes(n->d) > 160 * 1024) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network too large for one workgroup's LDS (160 KiB)");
   // landing points: every output time after t[0] plus every bucket edge strictly inside (t[0], t[T-1])
   std::vector<std::pair<double, int>> st;
   for (int k = 1; k < T; ++k) st.push_back({t_host[k], k});
@@ -377,9 +397,9 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
     a.loss_fail = fused->loss_fail; a.loss_sums = fused->loss_sums; a.loss_F = fused->loss_F; a.loss_rna_base = fused->loss_rna_base;
     for (int k = 0; k < 4; ++k) a.loss_lam[k] = fused->loss_lam[k];
     for (int k = 0; k < 3; ++k) a.loss_norm[k] = fused->loss_norm[k];
-    const bool can = !dp5 && pk_network_resolve_method(n, &o) == PK_METHOD_ARK436 && pk::net_arkp_fits(n->d, n->max_sites) && pk::net_arkp_fuses_loss();
-    if (!can) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: topologies 0 / 1 / 4 on the default additive integrator only; "
-                                                         "use pk_network_simulate_batch + pk_network_objective_batch");
+    if (!(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: topologies 0 / 1 / 4 on the default additive integrator only; "
+                                                "use pk_network_simulate_batch + pk_network_objective_batch");
   }
   if (hipSetDevice(pk_ctx_device(c)) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipSetDevice");
   hipStream_t stream = (hipStream_t)pk_ctx_stream(c);
@@ -404,42 +424,31 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       return pk_ctx_fail(c, PK_ERR_HIP, "hipMemcpy");
     a.stops_p = n->stops_dev; a.stop_out_p = n->stop_out_dev;
   }
-  if (ws) {
-    // ROS34PW2 on workspace slabs (pk_network_solve_ws.hpp): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
-    if (fused) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: not on the workspace kernel; use pk_network_simulate_batch + pk_network_objective_batch");
-    if (o.method == PK_METHOD_ARK436)
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: not on the workspace kernel (networks beyond one workgroup's LDS); use PK_METHOD_ROS34PW2");
-    struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; } q{&n->d, &a, (long long)B, 0};
-    if (pk::net_ws_grid(n->d, (long long)B, &q.grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
-    auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
-      const Q& r = *(const Q*)user;
-      return pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
-    };
-    return pk_ctx_scratch_launch(c, (size_t)q.grid * pk::net_ws_slab_doubles(n->d) * sizeof(double), launch, &q);
-  }
-  if (dp5) {
-    const size_t lb = pk::net_rk45_lds_bytes(n->d);
+  const int M = n->d.model;
+  switch (plan.kernel) {
+    case NetKernel::Workspace: {
+      // ROS34PW2 on workspace slabs (net_solve_ws_kernel): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
+      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; } q{&n->d, &a, (long long)B, 0};
+      if (pk::net_ws_grid(n->d, (long long)B, &q.grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+      auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
+        const Q& r = *(const Q*)user;
+        return pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
+      };
+      return pk_ctx_scratch_launch(c, (size_t)q.grid * pk::net_ws_slab_doubles(n->d) * sizeof(double), launch, &q);
+    }
+    case NetKernel::DP5: {
+      const size_t lb = pk::net_rk45_lds_bytes(n->d);
 #define PK_RK_LAUNCH(M)                                                                                                              \
-    do {                                                                                                                               \
-      if (lb > 48 * 1024) (void)hipFuncSetAttribute((const void*)pk::net_rk45_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb); \
-      hipLaunchKernelGGL(pk::net_rk45_kernel<M>, dim3((unsigned)B), dim3(256), lb, stream, n->d, a);                                   \
-    } while (0)
-    if (n->d.model == 0) PK_RK_LAUNCH(0); else if (n->d.model == 1) PK_RK_LAUNCH(1); else if (n->d.model == 2) PK_RK_LAUNCH(2); else PK_RK_LAUNCH(4);
+      do {                                                                                                                             \
+        if (lb > 48 * 1024) (void)hipFuncSetAttribute((const void*)pk::net_rk45_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb); \
+        hipLaunchKernelGGL(pk::net_rk45_kernel<M>, dim3((unsigned)B), dim3(256), lb, stream, n->d, a);                                 \
+      } while (0)
+      if (M == 0) PK_RK_LAUNCH(0); else if (M == 1) PK_RK_LAUNCH(1); else if (M == 2) PK_RK_LAUNCH(2); else PK_RK_LAUNCH(4);
 #undef PK_RK_LAUNCH
-    hipError_t er = hipGetLastError();
-    return er == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(er));
-  }
-  // Register-resident kernel (one thread per protein) when every block fits its per-thread arrays; opts->linsolve ==
-  // PK_LINSOLVE_STRUCTURED forces the LDS kernel (kept as the general fallback and as the A/B reference).
-  // ---- default integrator: ARK436 (order 4) in the one-thread-per-protein layout; ROS34PW2 (order 3) everywhere else / on request
-  {
-    const int threads_a = ((n->d.N + 63) / 64) * 64;
-    const int resolved = pk_network_resolve_method(n, &o);
-    if (resolved == PK_ERR_UNSUPPORTED)
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: <= 8 sites per protein and N <= 256 (topologies 0 / 1 / 4: <= 512 lanes of the dense layout); "
-                                                "combinatorial topology: <= 3 sites, N <= 256; use PK_METHOD_ROS34PW2");
-    const size_t lds_a = resolved == PK_METHOD_ARK436 ? pk::net_ark_lds_bytes(n->d, n->nnzT, n->max_sites, threads_a) : 0;
-    if (resolved == PK_METHOD_ARK436) {
+      break;
+    }
+    case NetKernel::ArkPair:
+    case NetKernel::Ark: {
       // The order-4 method runs at 0.25 x the requested tolerances: at that factor its error equals the order-3 method's at the SAME nominal
       // tolerance.  Measured at rtol = atol = 1e-8, band widths from the converged solution (tools/gpu_ark_population*.py, bench.py):
       //   BASELINE config 5's population (8 192 candidates, log-normal 0.5 around the defaults), fixture candidate vs LSODA@1e-12:
@@ -455,41 +464,40 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       static const double ctl_g = [] { const char* v = getenv("PK_ARK_GROW"); return v ? atof(v) : 0.0; }();
       aa.ctl_safety = ctl_s; aa.ctl_grow = ctl_g;
       // [r3] arrow topologies: the dense two-lanes-per-protein layout, every stage vector in registers (PK_ARK_PAIR=0: round 2's kernel)
-      const bool pair = pk::net_arkp_fits(n->d, n->max_sites);
-      hipError_t ea = pair ? pk::launch_net_arkp(n->d, aa, n->nnzT, n->max_sites, (long long)B, stream)
-                           : pk::launch_net_ark(n->d, aa, n->max_sites, (long long)B, threads_a, lds_a, stream);
-      if (ea == hipSuccess) ea = hipGetLastError();
-      return ea == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(ea));
+      const hipError_t ea = plan.kernel == NetKernel::ArkPair
+                                ? pk::launch_net_arkp(n->d, aa, n->nnzT, n->max_sites, (long long)B, stream)
+                                : pk::launch_net_ark(n->d, aa, n->max_sites, (long long)B, plan.threads,
+                                                     pk::net_ark_lds_bytes(n->d, n->nnzT, n->max_sites, plan.threads), stream);
+      if (ea != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(ea));
+      break;
     }
-  }
-  if (comb_reg && o.linsolve != PK_LINSOLVE_STRUCTURED) {
-    const int threads2 = ((n->d.N + 63) / 64) * 64;
-    if (n->max_sites <= 2) hipLaunchKernelGGL((pk::net_solve_reg2_kernel<2>), dim3((unsigned)B), dim3(threads2), n->solve_reg_lds_bytes, stream, n->d, a);
-    else                   hipLaunchKernelGGL((pk::net_solve_reg2_kernel<3>), dim3((unsigned)B), dim3(threads2), n->solve_reg_lds_bytes, stream, n->d, a);
-    hipError_t e2 = hipGetLastError();
-    return e2 == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(e2));
-  }
-  const bool reg_ok = n->d.model != 2 && n->d.N <= 256 && n->max_sites <= 8 && n->solve_reg_lds_bytes <= 64 * 1024 && o.linsolve != PK_LINSOLVE_STRUCTURED;
-  if (reg_ok) {
-    const int threads = ((n->d.N + 63) / 64) * 64;
-    const size_t lb = n->solve_reg_lds_bytes;
-#define PK_REG_LAUNCH(M, MS) hipLaunchKernelGGL((pk::net_solve_reg_kernel<M, MS>), dim3((unsigned)B), dim3(threads), lb, stream, n->d, a)
-    if (n->max_sites <= 4) {
-      if (n->d.model == 0) PK_REG_LAUNCH(0, 4); else if (n->d.model == 1) PK_REG_LAUNCH(1, 4); else PK_REG_LAUNCH(4, 4);
-    } else if (n->max_sites <= 6) {
-      if (n->d.model == 0) PK_REG_LAUNCH(0, 6); else if (n->d.model == 1) PK_REG_LAUNCH(1, 6); else PK_REG_LAUNCH(4, 6);
-    } else {
-      if (n->d.model == 0) PK_REG_LAUNCH(0, 8); else if (n->d.model == 1) PK_REG_LAUNCH(1, 8); else PK_REG_LAUNCH(4, 8);
-    }
+    case NetKernel::CombReg:
+      if (n->max_sites <= 2) hipLaunchKernelGGL((pk::net_solve_reg2_kernel<2>), dim3((unsigned)B), dim3(plan.threads), n->solve_reg_lds_bytes, stream, n->d, a);
+      else                   hipLaunchKernelGGL((pk::net_solve_reg2_kernel<3>), dim3((unsigned)B), dim3(plan.threads), n->solve_reg_lds_bytes, stream, n->d, a);
+      break;
+    case NetKernel::Reg: {
+      const size_t lb = n->solve_reg_lds_bytes;
+#define PK_REG_LAUNCH(M, MS) hipLaunchKernelGGL((pk::net_solve_reg_kernel<M, MS>), dim3((unsigned)B), dim3(plan.threads), lb, stream, n->d, a)
+      if (n->max_sites <= 4) {
+        if (M == 0) PK_REG_LAUNCH(0, 4); else if (M == 1) PK_REG_LAUNCH(1, 4); else PK_REG_LAUNCH(4, 4);
+      } else if (n->max_sites <= 6) {
+        if (M == 0) PK_REG_LAUNCH(0, 6); else if (M == 1) PK_REG_LAUNCH(1, 6); else PK_REG_LAUNCH(4, 6);
+      } else {
+        if (M == 0) PK_REG_LAUNCH(0, 8); else if (M == 1) PK_REG_LAUNCH(1, 8); else PK_REG_LAUNCH(4, 8);
+      }
 #undef PK_REG_LAUNCH
-  } else {
-    // LDS kernel: every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
-    int threads = (n->d.S <= 128 && n->d.N <= 64) ? 64 : 256;        // measured at S = 500: 256 threads beat 128 by 1.33x
-    if (const char* e = getenv("PK_NET_THREADS")) { const int v = atoi(e); if ((v == 64 || v == 128 || v == 256) && n->d.S <= 4 * v && n->d.N <= 2 * v) threads = v; }
-    if (n->d.model == 0)      hipLaunchKernelGGL(pk::net_solve_kernel<0>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
-    else if (n->d.model == 1) hipLaunchKernelGGL(pk::net_solve_kernel<1>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
-    else if (n->d.model == 2) hipLaunchKernelGGL(pk::net_solve_kernel<2>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
-    else                      hipLaunchKernelGGL(pk::net_solve_kernel<4>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
+      break;
+    }
+    case NetKernel::Lds: {
+      // every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
+      int threads = (n->d.S <= 128 && n->d.N <= 64) ? 64 : 256;        // measured at S = 500: 256 threads beat 128 by 1.33x
+      if (const char* e = getenv("PK_NET_THREADS")) { const int v = atoi(e); if ((v == 64 || v == 128 || v == 256) && n->d.S <= 4 * v && n->d.N <= 2 * v) threads = v; }
+      if (M == 0)      hipLaunchKernelGGL(pk::net_solve_kernel<0>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
+      else if (M == 1) hipLaunchKernelGGL(pk::net_solve_kernel<1>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
+      else if (M == 2) hipLaunchKernelGGL(pk::net_solve_kernel<2>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
+      else             hipLaunchKernelGGL(pk::net_solve_kernel<4>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
+      break;
+    }
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(e));

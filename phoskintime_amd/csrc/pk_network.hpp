@@ -113,7 +113,7 @@ __device__ __forceinline__ double fold_change(const double a, const double b) {
 // LDS work area of one candidate
 struct NetLds {
   double *p, *y, *Kt, *Sall, *Pvec, *synth, *dsyn;     // dsyn: d synth_i / d (TF . P_vec)_i   (Jacobian only)
-  __device__ static size_t doubles(const NetDev& n) { return (size_t)n.n_var + n.S + n.n_K + n.sites + 3 * (size_t)n.N; }
+  __host__ __device__ static size_t doubles(const NetDev& n) { return (size_t)n.n_var + n.S + n.n_K + n.sites + 3 * (size_t)n.N; }
   __device__ NetLds() {}
   __device__ NetLds(double* base, const NetDev& n) {
     p = base; y = p + n.n_var; Kt = y + n.S; Sall = Kt + n.n_K; Pvec = Sall + n.sites; synth = Pvec + n.N; dsyn = synth + n.N;

@@ -1,7 +1,8 @@
 // pk_network_solve.hpp -- batched integration of the network ODE: replaces global_model.simulate.simulate_odeint
 // (simulate.py:34-80: odeint(rhs_odeint, y0, t, Dfun = fd_jacobian_odeint, rtol, atol, mxstep)) for B candidates.
 //
-// One workgroup per candidate; state, stage vectors and per-block factors in LDS.
+// One workgroup per candidate; state, stage vectors and per-block factors in LDS (net_solve_kernel) or, for networks of any size, in a
+// slab of an HBM workspace (net_solve_ws_kernel).  Both kernels run the same body, net_rosw_solve, on two layouts of the thread's work.
 //
 // Integrator: ROS34PW2 (Rang & Angermann 2005), a 4-stage, order-3, stiffly accurate, L-stable Rosenbrock-W method --
 // its order conditions hold for ANY approximation of the Jacobian (table verified in 50-digit arithmetic,
@@ -84,13 +85,81 @@ __device__ __forceinline__ double err_acc(double a, double q, const bool rms) {
   return rms ? __builtin_fma(q, q, a) : ((q > a || q != q) ? q : a);
 }
 
-template <int MODEL>
-__global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const NetSolveArgs A) {
+
+// Per-candidate work area of the integrator: NetLds, then [Ys | U1..U4 | R | winv] (S each) and [sinv | cR | gP] (N each)
+__host__ __device__ inline size_t net_rosw_doubles(const NetDev& n) { return NetLds::doubles(n) + 7 * (size_t)n.S + 3 * (size_t)n.N; }
+
+// Where a thread finds the states and proteins it owns, and the TF CSR -- all that differs between the LDS and the workspace kernel.
+//   states(f): f(k, i, loc, st, ss, ns) for each state k of this thread (protein, position in its block, block start, site offset, sites)
+//   prots(f):  f(i, st, ss, ns, drv) for each protein i of this thread (block start, site offset, sites, driver_map entry)
+// Both visit k / i = tid, tid + nt, ... in increasing order.
+//
+// LDS kernel: up to KS states and KP proteins per thread, their contexts in registers (host guarantees S <= KS*nt, N <= KP*nt); TF CSR
+// cached in LDS by the kernel
+struct NetRegLayout {
+  static constexpr int KS = 4, KP = 2;
+  const double *tf_dat, *tf_deg; const int32_t *tf_ptr, *tf_idx;
+  int S, N;
+  int s_i[KS], s_loc[KS], s_st[KS], s_ss[KS], s_ns[KS];
+  int p_st[KP], p_ss[KP], p_ns[KP], p_drv[KP];
+  __device__ __forceinline__ NetRegLayout(const NetDev& n, const double* dat, const double* deg, const int32_t* ptr, const int32_t* idx)
+      : tf_dat(dat), tf_deg(deg), tf_ptr(ptr), tf_idx(idx), S(n.S), N(n.N) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+#pragma unroll
+    for (int q = 0; q < KS; ++q) {
+      const int k = tid + q * nt;
+      if (k < S) { const int i = n.state_prot[k]; s_i[q] = i; s_loc[q] = n.state_local[k]; s_st[q] = n.offset_y[i]; s_ss[q] = n.offset_s[i]; s_ns[q] = n.n_sites[i]; }
+      else { s_i[q] = 0; s_loc[q] = 0; s_st[q] = 0; s_ss[q] = 0; s_ns[q] = 0; }
+    }
+#pragma unroll
+    for (int q = 0; q < KP; ++q) {
+      const int i = tid + q * nt;
+      if (i < N) { p_st[q] = n.offset_y[i]; p_ss[q] = n.offset_s[i]; p_ns[q] = n.n_sites[i]; p_drv[q] = n.driver_map[i]; }
+      else { p_st[q] = 0; p_ss[q] = 0; p_ns[q] = 0; p_drv[q] = -1; }
+    }
+  }
+  template <class F> __device__ __forceinline__ void states(F&& f) const {
+#pragma unroll
+    for (int q = 0; q < KS; ++q) {
+      const int k = threadIdx.x + q * blockDim.x;
+      if (k >= S) break;
+      f(k, s_i[q], s_loc[q], s_st[q], s_ss[q], s_ns[q]);
+    }
+  }
+  template <class F> __device__ __forceinline__ void prots(F&& f) const {
+#pragma unroll
+    for (int q = 0; q < KP; ++q) {
+      const int i = threadIdx.x + q * blockDim.x;
+      if (i >= N) break;
+      f(i, p_st[q], p_ss[q], p_ns[q], p_drv[q]);
+    }
+  }
+};
+
+// workspace kernel: every thread strides over states and proteins (no register contexts, hence no ceiling); topology read from global
+struct NetWsLayout {
+  const NetDev& n;
+  const double *tf_dat, *tf_deg; const int32_t *tf_ptr, *tf_idx;
+  __device__ __forceinline__ explicit NetWsLayout(const NetDev& n_)
+      : n(n_), tf_dat(n_.TF_data), tf_deg(n_.tf_deg), tf_ptr(n_.TF_indptr), tf_idx(n_.TF_indices) {}
+  template <class F> __device__ __forceinline__ void states(F&& f) const {
+    for (int k = threadIdx.x; k < n.S; k += blockDim.x) {
+      const int i = n.state_prot[k];
+      f(k, i, n.state_local[k], n.offset_y[i], n.offset_s[i], n.n_sites[i]);
+    }
+  }
+  template <class F> __device__ __forceinline__ void prots(F&& f) const {
+    for (int i = threadIdx.x; i < n.N; i += blockDim.x) f(i, n.offset_y[i], n.offset_s[i], n.n_sites[i], n.driver_map[i]);
+  }
+};
+
+// ROS34PW2-W of candidate b, from loading x and y0 to the status / n_steps write.  L: the candidate's NetLds; base: its stage vectors
+// (net_rosw_doubles - NetLds::doubles of them); red: >= 24 doubles of LDS for the reductions.
+template <int MODEL, class Layout>
+__device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveArgs& A, const Layout& lay, const long long b, NetLds L,
+                                               double* const base, double* const red) {
   using namespace rosw;
   constexpr int model = MODEL;
-  extern __shared__ __align__(16) double lds[];
-  NetLds L(lds, n);
-  double* base = lds + NetLds::doubles(n);
   const int S = n.S, N = n.N;
   double* y = L.y;                        // current state
   double* Ys = base;                      // stage point
@@ -100,38 +169,15 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
   double* sinv = winv + S;                // per protein: 1 / Schur pivot of the P row (arrow blocks)
   double* cR = sinv + N;                  // per protein: d f_P / d R
   double* gP = cR + N;                    // per protein: saturating-kinetics factor 1 / (1 + P)^2 (1 otherwise)
-  double* red = gP + N;                   // 24 doubles: reductions
-  // static topology the inner loop touches, cached in LDS: TF CSR (data, degree, indptr, indices)
-  const int nnzT = n.TF_indptr[N];
-  double* tf_dat = red + 24;
-  double* tf_degl = tf_dat + nnzT;
-  int32_t* tf_ptr = reinterpret_cast<int32_t*>(tf_degl + N);
-  int32_t* tf_idx = tf_ptr + (N + 1);
+  const double* __restrict__ tf_dat = lay.tf_dat;
+  const double* __restrict__ tf_deg = lay.tf_deg;
+  const int32_t* __restrict__ tf_ptr = lay.tf_ptr;
+  const int32_t* __restrict__ tf_idx = lay.tf_idx;
   const NetSlices sl(n.n_K, N, n.sites);
-  const long long b = blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
   const double* stops = A.stops_p ? A.stops_p : A.stops_v;
   const int32_t* stop_out = A.stop_out_p ? A.stop_out_p : A.stop_out_v;
 
-  for (int k = tid; k < nnzT; k += nt) { tf_dat[k] = n.TF_data[k]; tf_idx[k] = n.TF_indices[k]; }
-  for (int k = tid; k <= N; k += nt) tf_ptr[k] = n.TF_indptr[k];
-  for (int k = tid; k < N; k += nt) tf_degl[k] = n.tf_deg[k];
-  // per-thread contexts in registers: up to KS states and KP proteins per thread (host guarantees S <= KS*nt, N <= KP*nt)
-  constexpr int KS = 4, KP = 2;
-  int s_i[KS], s_loc[KS], s_st[KS], s_ss[KS], s_ns[KS];
-#pragma unroll
-  for (int q = 0; q < KS; ++q) {
-    const int k = tid + q * nt;
-    if (k < S) { const int i = n.state_prot[k]; s_i[q] = i; s_loc[q] = n.state_local[k]; s_st[q] = n.offset_y[i]; s_ss[q] = n.offset_s[i]; s_ns[q] = n.n_sites[i]; }
-    else { s_i[q] = 0; s_loc[q] = 0; s_st[q] = 0; s_ss[q] = 0; s_ns[q] = 0; }
-  }
-  int p_st[KP], p_ss[KP], p_ns[KP], p_drv[KP];
-#pragma unroll
-  for (int q = 0; q < KP; ++q) {
-    const int i = tid + q * nt;
-    if (i < N) { p_st[q] = n.offset_y[i]; p_ss[q] = n.offset_s[i]; p_ns[q] = n.n_sites[i]; p_drv[q] = n.driver_map[i]; }
-    else { p_st[q] = 0; p_ss[q] = 0; p_ns[q] = 0; p_drv[q] = -1; }
-  }
   const double* xb = A.x + b * n.n_var;
   for (int k = tid; k < n.n_var; k += nt) L.p[k] = A.x_is_raw ? softplus(xb[k]) : xb[k];
   const double* y0 = A.y0 + (A.y0_batched ? b * S : 0);
@@ -141,11 +187,7 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
 
   // ---- block factorisation of  g I - J_blockdiag(y)  and block solve  x <- W^{-1} r  (in place: r -> x), one thread per protein
   auto factor = [&](const double g) {
-#pragma unroll
-    for (int q_ = 0; q_ < KP; ++q_) {
-      const int i = tid + q_ * nt;
-      if (i >= N) break;
-      const int st = p_st[q_], ss = p_ss[q_], ns = p_ns[q_];
+    lay.prots([&](const int i, const int st, const int ss, const int ns, const int) {
       const double Bi = L.p[sl.B + i], Ci = L.p[sl.C + i], Di = L.p[sl.D + i], Ei = L.p[sl.E + i];
       const double* Dp = L.p + sl.Dp + ss;
       const double* Sr = L.Sall + ss;
@@ -187,15 +229,11 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
         }
         sinv[i] = 1.0 / (g + Di + sumS * g_p - acc);
       }
-    }
+    });
     __syncthreads();
   };
   auto block_solve = [&](const double* r, double* x) {
-#pragma unroll
-    for (int q_ = 0; q_ < KP; ++q_) {
-      const int i = tid + q_ * nt;
-      if (i >= N) break;
-      const int st = p_st[q_], ss = p_ss[q_], ns = p_ns[q_];
+    lay.prots([&](const int i, const int st, const int ss, const int ns, const int) {
       const double Ei = L.p[sl.E + i];
       const double* Sr = L.Sall + ss;
       const double xR = r[st] * winv[st];
@@ -228,32 +266,26 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
         x[st + 1] = xP;
         for (int j = 0; j < ns; ++j) x[st + 2 + j] += (Sr[j] * g_p) * winv[st + 2 + j] * xP;
       }
-    }
+    });
     __syncthreads();
   };
-  // P_vec -> TF input -> synthesis rate for the state L.y points at (net_prepare_state with the LDS-cached topology)
+  // P_vec -> TF input -> synthesis rate for the state L.y points at (net_prepare_state with the layout's topology)
   auto prepare_state = [&]() {
-#pragma unroll
-    for (int q = 0; q < KP; ++q) {
-      const int i = tid + q * nt;
-      if (i >= N) break;
+    lay.prots([&](const int i, const int st, const int, const int ns, const int drv) {
       double tot;
-      if (model != 2 && p_drv[q] >= 0) tot = L.Kt[p_drv[q]];        // the combinatorial RHS ignores driver_map (jacspeedup.py:319-327)
-      else { tot = 0.0; const int cnt = (model == 2) ? (1 << p_ns[q]) : 1 + p_ns[q]; for (int m_ = 0; m_ < cnt; ++m_) tot += L.y[p_st[q] + 1 + m_]; }
+      if (model != 2 && drv >= 0) tot = L.Kt[drv];                  // the combinatorial RHS ignores driver_map (jacspeedup.py:319-327)
+      else { tot = 0.0; const int cnt = (model == 2) ? (1 << ns) : 1 + ns; for (int m_ = 0; m_ < cnt; ++m_) tot += L.y[st + 1 + m_]; }
       L.Pvec[i] = tot;
-    }
+    });
     __syncthreads();
     const double ts = L.p[sl.tf];
-#pragma unroll
-    for (int q = 0; q < KP; ++q) {
-      const int i = tid + q * nt;
-      if (i >= N) break;
+    lay.prots([&](const int i, const int, const int, const int, const int) {
       double acc = 0.0;
       for (int e_ = tf_ptr[i]; e_ < tf_ptr[i + 1]; ++e_) acc += tf_dat[e_] * L.Pvec[tf_idx[e_]];
-      double v = acc / tf_degl[i];
+      double v = acc / tf_deg[i];
       if (model != 4) v = v / (1.0 + fabs(v));
       L.synth[i] = synth_rate(L.p[sl.A + i], ts, v, nullptr);
-    }
+    });
     __syncthreads();
   };
   int status = PK_ST_OK, nacc = 0, nrej = 0;
@@ -285,30 +317,26 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
       if (!(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= PK_ST_HMIN; break; }
       const double hinv = 1.0 / hs;
       factor(hinv * (1.0 / GAM));
-      // four stages, one loop body (kept rolled: the body is large and register-hungry when replicated)
-      double* const Us[4] = {U1, U2, U3, U4};
+      // four stages, one loop body (kept rolled: the body is large and register-hungry when replicated); stage j's vector is U1 + j S
 #pragma unroll 1
       for (int sg = 0; sg < 4; ++sg) {
         if (sg > 0) {
           for (int k = tid; k < S; k += nt) {
             double v = y[k];
-            for (int j = 0; j < sg; ++j) v = __builtin_fma(TA[sg][j], Us[j][k], v);
+            for (int j = 0; j < sg; ++j) v = __builtin_fma(TA[sg][j], U1[(size_t)j * S + k], v);
             Ys[k] = v;
           }
           __syncthreads();
         }
         L.y = (sg == 0) ? y : Ys;
         prepare_state();
-#pragma unroll
-        for (int q = 0; q < KS; ++q) {
-          const int k = tid + q * nt;
-          if (k >= S) break;
-          double v = net_state_rhs_ctx<MODEL>(n, L, s_i[q], s_loc[q], s_st[q], s_ss[q], s_ns[q]);
-          for (int j = 0; j < sg; ++j) v = __builtin_fma(TC[sg][j] * hinv, Us[j][k], v);
+        lay.states([&](const int k, const int i, const int loc, const int st, const int ss, const int ns) {
+          double v = net_state_rhs_ctx<MODEL>(n, L, i, loc, st, ss, ns);
+          for (int j = 0; j < sg; ++j) v = __builtin_fma(TC[sg][j] * hinv, U1[(size_t)j * S + k], v);
           R_[k] = v;
-        }
+        });
         __syncthreads();
-        block_solve(R_, Us[sg]);
+        block_solve(R_, U1 + (size_t)sg * S);
       }
       // y1 = Ys + U4 ; err
       double e = 0.0;
@@ -369,9 +397,43 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
   }
 }
 
-__device__ __host__ inline size_t net_solve_lds_doubles(const NetDev& n) {
-  return ((size_t)n.n_var + n.S + n.n_K + n.sites + 3 * (size_t)n.N) + 7 * (size_t)n.S + 3 * (size_t)n.N + 24;
+// One workgroup per candidate, everything in dynamic LDS: the work area, 24 doubles of reductions, then the TF CSR
+template <int MODEL>
+__global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const NetSolveArgs A) {
+  extern __shared__ __align__(16) double lds[];
+  const int N = n.N, nnzT = n.TF_indptr[N];
+  double* red = lds + net_rosw_doubles(n);
+  double* tf_dat = red + 24;
+  double* tf_deg = tf_dat + nnzT;
+  int32_t* tf_ptr = reinterpret_cast<int32_t*>(tf_deg + N);
+  int32_t* tf_idx = tf_ptr + (N + 1);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int k = tid; k < nnzT; k += nt) { tf_dat[k] = n.TF_data[k]; tf_idx[k] = n.TF_indices[k]; }
+  for (int k = tid; k <= N; k += nt) tf_ptr[k] = n.TF_indptr[k];
+  for (int k = tid; k < N; k += nt) tf_deg[k] = n.tf_deg[k];
+  const NetRegLayout lay(n, tf_dat, tf_deg, tf_ptr, tf_idx);
+  net_rosw_solve<MODEL>(n, A, lay, blockIdx.x, NetLds(lds, n), lds + NetLds::doubles(n), red);
 }
+
+// Networks of any size: every per-candidate vector in a slab of an HBM workspace instead of LDS, so nothing limits S or N but device
+// memory.  The grid is persistent -- min(B, resident workgroups) -- and each workgroup loops over candidates, so the workspace is
+// grid x slab whatever B is.  A slab is the net_rosw_doubles work area padded to whole 128-B lines so that no two workgroups share a line;
+// LDS holds only the reduction buffer.  Visibility inside a workgroup: the __syncthreads() between phases (workgroup-scope release /
+// acquire), exactly as in the LDS kernel; no workgroup reads another's slab.
+template <int MODEL>
+__global__ __launch_bounds__(256) void net_solve_ws_kernel(const NetDev n, const NetSolveArgs A, const long long B, double* __restrict__ ws,
+                                                           const size_t slab) {
+  __shared__ double red[24];
+  double* const base0 = ws + (size_t)blockIdx.x * slab;
+  const NetWsLayout lay(n);
+  for (long long b = blockIdx.x; b < B; b += gridDim.x) {
+    __syncthreads();                                   // the previous candidate of this workgroup is done with the slab
+    net_rosw_solve<MODEL>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red);
+  }
+}
+
+__host__ __device__ inline size_t net_ws_slab_doubles(const NetDev& n) { return (net_rosw_doubles(n) + 15) / 16 * 16; }
+__device__ __host__ inline size_t net_solve_lds_doubles(const NetDev& n) { return net_rosw_doubles(n) + 24; }
 // + the LDS copy of the TF CSR: nnz doubles + N doubles + (N + 1 + nnz) int32 (rounded up to doubles)
 __host__ inline size_t net_solve_lds_bytes(const NetDev& n, int nnzT) {
   return (net_solve_lds_doubles(n) + (size_t)nnzT + n.N) * 8 + (((size_t)n.N + 1 + nnzT) * 4 + 7) / 8 * 8;

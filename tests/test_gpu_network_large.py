@@ -1,4 +1,4 @@
-"""GPU: networks beyond one workgroup's LDS (S > 1024, N > 512) on the HBM-workspace ROS34PW2-W kernel (csrc/pk_network_solve_ws.hpp).
+"""GPU: networks beyond one workgroup's LDS (S > 1024, N > 512) on the HBM-workspace ROS34PW2-W kernel (net_solve_ws_kernel, csrc/pk_network_solve.hpp).
 Truth comes from the reference: the union of 6 copies of a ``netlarge_m*`` fixture (``synthetic.tile_network``) integrates copy by
 copy like the fixture's network, whose LSODA run at 1e-12 (``Y_tight``) the reference produced."""
 from pathlib import Path

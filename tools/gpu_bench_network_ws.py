@@ -1,4 +1,5 @@
-"""Throughput of the HBM-workspace network integrator (csrc/pk_network_solve_ws.hpp), one JSON line per case (dev tool, run on an MI355X).
+"""Throughput of the HBM-workspace network integrator (net_solve_ws_kernel in csrc/pk_network_solve.hpp), one JSON line per case
+(dev tool, run on an MI355X).
 
   python tools/gpu_bench_network_ws.py [case ...]     cases: union, n10k, s1000 (default: all); B comes from the case table
 
