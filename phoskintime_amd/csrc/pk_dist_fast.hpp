@@ -1,4 +1,5 @@
-// pk_dist_fast.hpp -- throughput kernel for the distributive model (models/distmod.py:7-65), adaptive RODAS4 / LRP8.
+// pk_dist_fast.hpp -- throughput kernel for the distributive model (models/distmod.py:7-65), adaptive resolvent-form one-step
+// methods (RODAS4, LRP8, LRP12: ResolventTab).
 //
 // Same integrator, same arithmetic per state as solve_kernel<M_DIST, G, RODAS4, true> (arrow elimination), but laid
 // out for the VALU instead of for generality -- measured on MI355X the generic kernel spends its time in the LDS
@@ -42,38 +43,80 @@ __device__ __forceinline__ Trk<RPL> trk_scale(const double a, const Trk<RPL>& u)
   return r;
 }
 
+// What is uniform over a launch and chosen by run-time fields of SolveArgs, as a compile-time configuration.  DistFixed names one
+// combination (the launchers pick it when SolveArgs matches); DistAny reads every choice from SolveArgs at run time and serves the rest.
+//   metric class: none / running sum only (total_signal, mean_activity) / second moments and first differences (the other metrics)
+enum { PK_DM_NONE = 0, PK_DM_SUM = 1, PK_DM_FULL = 2 };
+__host__ __device__ __forceinline__ int dist_metric_class(const SolveArgs& A) {
+  return !A.metric ? PK_DM_NONE : (A.metric_id == PK_METRIC_TOTAL_SIGNAL || A.metric_id == PK_METRIC_MEAN_ACTIVITY) ? PK_DM_SUM : PK_DM_FULL;
+}
+template <bool CLIP, bool NORM, bool FLAT, bool SOL, int MC>
+struct DistFixed {
+  static constexpr int SLOT_MC = MC;                 // which bookkeeping slots exist (Parked)
+  __host__ __device__ static __forceinline__ bool clip(const SolveArgs&) { return CLIP; }
+  __host__ __device__ static __forceinline__ bool normalize(const SolveArgs&) { return NORM; }
+  __host__ __device__ static __forceinline__ bool flat(const SolveArgs&) { return FLAT; }
+  __host__ __device__ static __forceinline__ bool sol(const SolveArgs&) { return SOL; }
+  __host__ __device__ static __forceinline__ int mclass(const SolveArgs&) { return MC; }
+  static bool matches(const SolveArgs& A) {
+    return (A.clip != 0) == CLIP && (A.normalize != 0) == NORM && (A.flat != nullptr) == FLAT && (A.sol != nullptr) == SOL && dist_metric_class(A) == MC;
+  }
+};
+struct DistAny {
+  static constexpr int SLOT_MC = PK_DM_FULL;
+  __host__ __device__ static __forceinline__ bool clip(const SolveArgs& A) { return A.clip != 0; }
+  __host__ __device__ static __forceinline__ bool normalize(const SolveArgs& A) { return A.normalize != 0; }
+  __host__ __device__ static __forceinline__ bool flat(const SolveArgs& A) { return A.flat != nullptr; }
+  __host__ __device__ static __forceinline__ bool sol(const SolveArgs& A) { return A.sol != nullptr; }
+  __host__ __device__ static __forceinline__ int mclass(const SolveArgs& A) { return dist_metric_class(A); }
+  static bool matches(const SolveArgs&) { return true; }
+};
+// the combinations the library's own callers produce (batch.solve_ode_batch): trajectories + a running-sum metric (the Morris scan),
+// trajectories alone, the flat observable vector alone (the fits); all clipped, none normalised
+using DistSolSum = DistFixed<true, false, false, true, PK_DM_SUM>;
+using DistSolOnly = DistFixed<true, false, false, true, PK_DM_NONE>;
+using DistFlatOnly = DistFixed<true, false, true, false, PK_DM_NONE>;
+
+// number of per-lane slots: site rates S_i and 1 + D_i always; the running sum from PK_DM_SUM on; previous outputs, second moment, first
+// differences and shift only in PK_DM_FULL
+template <int RPL, int MC> constexpr int dist_fast_slots() { return MC == PK_DM_FULL ? 3 * RPL + 6 : MC == PK_DM_SUM ? 2 * RPL + 1 : 2 * RPL; }
+
 // Per-lane values that are touched once per step (site rates) or once per output (metric bookkeeping).  In registers by default;
-// PARK = true keeps them in LDS (slot-major: slot * 256 + thread, conflict-free), which frees 6 * RPL + 12 VGPRs: what lets the
+// PARK = true keeps them in LDS (slot-major: slot * NT + thread, conflict-free), which frees up to 6 * RPL + 12 VGPRs: what lets the
 // 4-lane x 8-row layout (30 % fewer instructions per replica than 8 x 4) run two waves per SIMD instead of one.
-template <int RPL, bool PARK> struct Parked;
-template <int RPL> struct Parked<RPL, false> {
+template <int RPL, bool PARK, int NT> struct Parked;
+template <int RPL, int NT> struct Parked<RPL, false, NT> {
   double v[3 * RPL + 6];
   __device__ __forceinline__ explicit Parked(double*) {}
   template <int K> __device__ __forceinline__ double get() const { return v[K]; }
   template <int K> __device__ __forceinline__ void set(double x) { v[K] = x; }
 };
-template <int RPL> struct Parked<RPL, true> {
+template <int RPL, int NT> struct Parked<RPL, true, NT> {
   double* base;
   __device__ __forceinline__ explicit Parked(double* lds) : base(lds + threadIdx.x) {}
-  template <int K> __device__ __forceinline__ double get() const { return base[K * 256]; }
-  template <int K> __device__ __forceinline__ void set(double x) { base[K * 256] = x; }
+  template <int K> __device__ __forceinline__ double get() const { return base[K * NT]; }
+  template <int K> __device__ __forceinline__ void set(double x) { base[K * NT] = x; }
 };
-template <int RPL, bool PARK> constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(3 * RPL + 6) * 256 * sizeof(double) : 0; }
+template <int RPL, bool PARK, int NT = 256, class CFG = DistAny>
+constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)dist_fast_slots<RPL, CFG::SLOT_MC>() * NT * sizeof(double) : 0; }
 
-template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1)>
-__global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A) {
+// NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
+template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny>
+__global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) {
   using Tab = ResolventTab<METHOD>;
   extern __shared__ __align__(16) double park_lds[];
-  Parked<RPL, PARK> pk(park_lds);
-  // slots: [0, RPL) S_i ; [RPL, 2 RPL) 1 + D_i ; [2 RPL, 3 RPL) previous site outputs ; then prevR, prevP, m1, m2, mdyn, shift
-  constexpr int K_SR = 0, K_DG = RPL, K_PS = 2 * RPL, K_PR = 3 * RPL, K_PP = 3 * RPL + 1, K_M1 = 3 * RPL + 2, K_M2 = 3 * RPL + 3,
-                K_MD = 3 * RPL + 4, K_SH = 3 * RPL + 5;
-  constexpr int RPB = 256 / G;
+  Parked<RPL, PARK, NT> pk(park_lds);
+  // slots: [0, RPL) S_i ; [RPL, 2 RPL) 1 + D_i ; then m1 (PK_DM_SUM), or previous site outputs, prevR, prevP, m1, m2, mdyn, shift (PK_DM_FULL)
+  constexpr int MCS = CFG::SLOT_MC;
+  constexpr int K_SR = 0, K_DG = RPL, K_PS = 2 * RPL, K_PR = 3 * RPL, K_PP = 3 * RPL + 1, K_M1 = (MCS == PK_DM_FULL ? 3 * RPL + 2 : 2 * RPL),
+                K_M2 = 3 * RPL + 3, K_MD = 3 * RPL + 4, K_SH = 3 * RPL + 5;
+  constexpr int RPB = NT / G;
   const int lane = lane_id();
   const int l = threadIdx.x & (G - 1);
   const long long rep = (long long)blockIdx.x * RPB + (threadIdx.x / G);
   if (rep >= A.B) return;
   const int n = A.n_sites, S = A.S, T = A.T;
+  const int mclass = CFG::mclass(A);
   const double* __restrict__ th = A.theta + rep * A.P;
 
   // ---- coefficients: uniform (A, B, C, D + sum S) and per site (S_i, 1 + D_i); padding sites are inert (S = 0, d = 1)
@@ -104,21 +147,24 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
   y.sg = gsum<G>(lsum, lane);
 
   // ---- output / fused Morris metric (same semantics as Emitter in pk_solve_kernel.hpp)
-  static_for<RPL + 6>([&](auto kc) { pk.template set<K_PS + decltype(kc)::value>(0.0); });
+  static_for<dist_fast_slots<RPL, MCS>() - 2 * RPL>([&](auto kc) { pk.template set<K_PS + decltype(kc)::value>(0.0); });
   const int T5 = T > 5 ? T - 5 : 0;
-  auto emit = [&](const int k, const Trk<RPL>& v, const bool nan_fill) {
-    double* solp = A.sol ? A.sol + (rep * T + k) * S : nullptr;
-    double* fl = A.flat ? A.flat + rep * A.F : nullptr;
+  // this lane's first site in the trajectory row of the next output time; advanced by one row per landing
+  double* srow = CFG::sol(A) ? A.sol + rep * T * S + 2 + l : nullptr;
+  // one output row: nf = std::true_type writes the NaN rows of a failed replica (cold), std::false_type the values of v
+  auto emit = [&](const int k, const Trk<RPL>& v, auto nf) {
+    constexpr bool nan_fill = decltype(nf)::value;
+    double* fl = CFG::flat(A) ? A.flat + rep * A.F : nullptr;
     auto val = [&](double x, int state) {
       if (nan_fill) return __builtin_nan("");
-      double r = A.clip ? ((x < 0.0) ? 0.0 : x) : x;
-      if (A.normalize) r *= 1.0 / y0p[state];
+      double r = CFG::clip(A) ? ((x < 0.0) ? 0.0 : x) : x;
+      if (CFG::normalize(A)) r *= 1.0 / y0p[state];
       return r;
     };
     const double vR = val(v.R, 0), vP = val(v.P, 1);
     if (l == 0) {
-      if (solp) { solp[0] = vR; solp[1] = vP; }
-      if (fl) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
+      if (CFG::sol(A)) { srow[-2] = vR; srow[-1] = vP; }
+      if (CFG::flat(A)) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
     }
     double vs[RPL];
     double loc = (l == 0) ? vR + vP : 0.0;
@@ -127,17 +173,17 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
       const int i = l + G * j;
       vs[j] = (i < n) ? val(v.s[j], 2 + i) : 0.0;
       if (i < n) {
-        if (solp) solp[2 + i] = vs[j];
-        if (fl) fl[T5 + T + i * T + k] = vs[j];
+        if (CFG::sol(A)) srow[G * j] = vs[j];
+        if (CFG::flat(A)) fl[T5 + T + i * T + k] = vs[j];
       }
       loc += vs[j];
     }
-    if (A.metric) {
+    if (CFG::sol(A)) srow += S;
+    if (mclass != PK_DM_NONE) {
       // total_signal / mean_activity need the running sum only; the second-moment and first-difference bookkeeping (and its LDS
-      // traffic in the parked layouts) runs only for the metrics that use it -- metric_id is uniform across the launch
-      const bool sum_only = (A.metric_id == PK_METRIC_TOTAL_SIGNAL || A.metric_id == PK_METRIC_MEAN_ACTIVITY);
+      // traffic in the parked layouts) exists only for the metrics that use it
       pk.template set<K_M1>(pk.template get<K_M1>() + loc);
-      if (!sum_only) {
+      if constexpr (MCS == PK_DM_FULL) if (mclass == PK_DM_FULL) {
         double m2 = pk.template get<K_M2>(), mdyn = pk.template get<K_MD>(), shift = pk.template get<K_SH>();
         double prevR = pk.template get<K_PR>(), prevP = pk.template get<K_PP>();
         if (k == 0) {
@@ -167,17 +213,18 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
     }
   };
   auto finish = [&](const int status, const int acc, const int rej) {
-    if (A.metric) {
-      const double m1 = pk.template get<K_M1>(), m2 = pk.template get<K_M2>(), mdyn = pk.template get<K_MD>(), shift = pk.template get<K_SH>();
+    if (mclass != PK_DM_NONE) {
       const double L = 2.0 * T + (double)T * n;
-      const double tot = gsum<G>(m1, lane);
-      double m;
-      switch (A.metric_id) {
-        case PK_METRIC_TOTAL_SIGNAL: m = tot; break;
-        case PK_METRIC_MEAN_ACTIVITY: m = tot / L; break;
-        case PK_METRIC_VARIANCE: { const double q = gsum<G>(m2, lane); const double ms = tot / L - shift; m = q / L - ms * ms; } break;
-        case PK_METRIC_DYNAMICS: m = gsum<G>(mdyn, lane); break;
-        default: { const double q = gsum<G>(m2, lane); m = sqrt(fmax(q + 2.0 * shift * tot - L * shift * shift, 0.0)); } break;
+      const double tot = gsum<G>(pk.template get<K_M1>(), lane);
+      double m = tot;
+      if (A.metric_id == PK_METRIC_MEAN_ACTIVITY) m = tot / L;
+      if constexpr (MCS == PK_DM_FULL) if (mclass == PK_DM_FULL) {
+        const double m2 = pk.template get<K_M2>(), mdyn = pk.template get<K_MD>(), shift = pk.template get<K_SH>();
+        switch (A.metric_id) {
+          case PK_METRIC_VARIANCE: { const double q = gsum<G>(m2, lane); const double ms = tot / L - shift; m = q / L - ms * ms; } break;
+          case PK_METRIC_DYNAMICS: m = gsum<G>(mdyn, lane); break;
+          default: { const double q = gsum<G>(m2, lane); m = sqrt(fmax(q + 2.0 * shift * tot - L * shift * shift, 0.0)); } break;
+        }
       }
       if (l == 0) A.metric[rep] = m;
     }
@@ -186,9 +233,8 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
       if (A.n_steps) { A.n_steps[2 * rep] = acc; A.n_steps[2 * rep + 1] = rej; }
     }
   };
-  auto fail_from = [&](int k) { for (; k < T; ++k) emit(k, y, true); };
 
-  emit(0, y, false);
+  emit(0, y, std::false_type{});
   int status = PK_ST_OK, nacc = 0, nrej = 0;
   if (T < 2) { finish(status, 0, 0); return; }
 
@@ -220,12 +266,10 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
   double h;
   {
     const Trk<RPL> f0 = rhs_of(y);
-    Trk<RPL> one = y;                                 // |y| / sc and |f0| / sc with sc = atol + rtol |y|
-    const double d0 = group_max(y, y, y), d1 = group_max(f0, y, y);
+    const double d0 = group_max(y, y, y), d1 = group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;
-    (void)one;
   }
 
   // Arrow factors of M = I - q J (q = gamma h) for the current step size.
@@ -258,13 +302,18 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
   };
 
   // resolvent-form step (the right-hand side is affine): z_1 = M^{-1} h f(y), z_{k+1} = M^{-1} z_k,
-  //   y_new = y + sum_k B_k z_k ,  err = sum_k E_k z_k     (ResolventTab: RODAS4 or LRP8)
+  //   y_new = y + sum_k B_k z_k ,  err = sum_k E_k z_k     (ResolventTab: RODAS4, LRP8 or LRP12)
   bool after_reject = false;
+  // vmcnt(0) alone: every load of the prologue has landed before the loop, so the loop's own wait is the one for tnx at a landing and
+  // no step waits for the stores of the landing before it
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   while (true) {
-    if (nacc + nrej >= A.max_steps) { status |= PK_ST_MAXSTEPS; fail_from(k); break; }
+    const double tnx = A.t[k + 1 < T ? k + 1 : T - 1];   // the output time after te, fetched a whole step before a landing can need it
+    // failure exits (step budget, vanishing step): status is set here and the NaN rows are written after the loop
+    const bool over = nacc + nrej >= A.max_steps;
     const bool last = (tc + 1.0001 * h >= te);
     const double hs = last ? te - tc : ((tc + 2.0 * h > te) ? 0.5 * (te - tc) : h);
-    if (!(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= PK_ST_HMIN; fail_from(k); break; }
+    if (over || !(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= over ? PK_ST_MAXSTEPS : PK_ST_HMIN; break; }
     factor(Tab::GAM * hs);
 
     Trk<RPL> z = solve(trk_scale(hs, rhs_of(y)));
@@ -282,38 +331,37 @@ __global__ __launch_bounds__(256, MINB) void dist_fast_kernel(const SolveArgs A)
       ++nrej; after_reject = true; h = 0.1 * hs;
       const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
       if (bad != 0.0 || (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC)) || (nonfinite(Dsum)) || (nonfinite(Scw))) {
-        status |= PK_ST_NONFINITE; fail_from(k); break;
+        status |= PK_ST_NONFINITE; break;
       }
       continue;
     }
     double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
     fac = fmax(1.0 / 6.0, fmin(5.0, fac));
     double hnew = hs * fast_rcp(fac);
-    if (err <= 1.0) {
-      ++nacc;
-      y = yn; tc += hs;
-      if (after_reject) hnew = fmin(hnew, hs);
-      after_reject = false;
-      if (last) {
-        tc = te;
-        // re-sum the sites at every landing so the tracked sum cannot drift
-        double loc = 0.0;
+    // accept / reject / landing bookkeeping as selects on per-lane predicates: what a wave runs here does not depend on which of its
+    // replicas accept or land
+    const bool acc = (err <= 1.0), land = acc && last;
+    nacc += acc ? 1 : 0; nrej += acc ? 0 : 1;
+    if (acc && after_reject) hnew = fmin(hnew, hs);
+    after_reject = !acc;
+    if (acc) y = yn;
+    tc = land ? te : (acc ? tc + hs : tc);
+    h = (land && hs < h) ? fmax(hnew, h) : hnew;
+    if (land) {
+      te = tnx;
+      asm volatile("" : "+v"(te));                      // pins this copy ahead of the row's stores: its wait then covers the load of tnx alone
+      // re-sum the sites at every landing so the tracked sum cannot drift
+      double loc = 0.0;
 #pragma unroll
-        for (int j = 0; j < RPL; ++j) loc += y.s[j];
-        y.sg = gsum<G>(loc, lane);
-        emit(k, y, false);
-        ++k;
-        h = (hs < h) ? fmax(hnew, h) : hnew;
-        if (k >= T) break;
-        te = A.t[k];
-      } else {
-        h = hnew;
-      }
-    } else {
-      ++nrej; after_reject = true;
-      h = hnew;
+      for (int j = 0; j < RPL; ++j) loc += y.s[j];
+      y.sg = gsum<G>(loc, lane);
+      emit(k, y, std::false_type{});
+      ++k;
     }
+    if (k >= T) break;
   }
+  if (status != PK_ST_OK)                               // a failed replica: NaN rows from the landing it failed at
+    for (; k < T; ++k) emit(k, y, std::true_type{});
   finish(status, nacc, nrej);
 }
 

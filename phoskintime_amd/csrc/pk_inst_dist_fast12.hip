@@ -13,30 +13,47 @@
 
 namespace pk {
 
-template <int G, int RPL>
-static void launch_plain(const SolveArgs& a, hipStream_t st) {
-  const long long rpb = 256 / G;
+// One instantiation: NT threads per workgroup, launch-uniform choices CFG (pk_dist_fast.hpp).
+template <int G, int RPL, bool PARK, int NT, class CFG>
+static void launch_cfg(const SolveArgs& a, hipStream_t st) {
+  const long long rpb = NT / G;
   const long long nblk = (a.B + rpb - 1) / rpb;
-  hipLaunchKernelGGL((dist_fast_kernel<G, RPL, PK_METHOD_LRP12>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+  constexpr size_t lds = dist_fast_lds_bytes<RPL, PARK, NT, CFG>();
+  auto kern = dist_fast_kernel<G, RPL, PK_METHOD_LRP12, PARK, (PARK ? 2 : 1), NT, CFG>;
+  if constexpr (lds > 48 * 1024) {
+    static const bool once = [kern] {
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      return true;
+    }();
+    (void)once;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(NT), lds, st, a);
+}
+
+// The combinations the library's own callers produce get a kernel with those choices compiled in (no dead output paths, no bookkeeping
+// slots they do not use); every other combination runs the kernel that reads them from SolveArgs.
+template <int G, int RPL, bool PARK, int NT>
+static void launch_nt(const SolveArgs& a, hipStream_t st) {
+  if (DistSolSum::matches(a)) launch_cfg<G, RPL, PARK, NT, DistSolSum>(a, st);
+  else if (DistSolOnly::matches(a)) launch_cfg<G, RPL, PARK, NT, DistSolOnly>(a, st);
+  else if (DistFlatOnly::matches(a)) launch_cfg<G, RPL, PARK, NT, DistFlatOnly>(a, st);
+  else launch_cfg<G, RPL, PARK, NT, DistAny>(a, st);
 }
 
 template <int G, int RPL>
-static void launch_parked(const SolveArgs& a, hipStream_t st) {
-  const long long rpb = 256 / G;
-  const long long nblk = (a.B + rpb - 1) / rpb;
-  constexpr size_t lds = dist_fast_lds_bytes<RPL, true>();
-  static const bool once = [] {
-    (void)hipFuncSetAttribute((const void*)dist_fast_kernel<G, RPL, PK_METHOD_LRP12, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL((dist_fast_kernel<G, RPL, PK_METHOD_LRP12, true, 2>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-}
+static void launch_plain(const SolveArgs& a, hipStream_t st) { launch_nt<G, RPL, false, 256>(a, st); }
+
+// parked layouts: one wave per workgroup -- a workgroup keeps its LDS and its place on the CU until its slowest wave is done, and the step
+// counts of the replicas differ (35-46 on the benchmark's batch), so wave-sized workgroups let the dispatcher refill each wave slot as it ends
+template <int G, int RPL>
+static void launch_parked(const SolveArgs& a, hipStream_t st) { launch_nt<G, RPL, true, 64>(a, st); }
 
 void launch_dist_fast12(const SolveArgs& a, hipStream_t st) {
   const int n = a.n_sites;
-  // dev A/B: PK_DIST_LAYOUT=8x4 forces the register-only 8 x 4 layout for 17 <= n <= 32
+  // dev A/B: PK_DIST_LAYOUT=8x4 forces the register-only 8 x 4 layout for 17 <= n <= 32; PK_DIST_LAYOUT=wg256 runs the 4 x 8 parked
+  // layout (29 <= n <= 32) in 256-thread workgroups
   static const bool force84 = getenv("PK_DIST_LAYOUT") && !strcmp(getenv("PK_DIST_LAYOUT"), "8x4");
+  static const bool wg256 = getenv("PK_DIST_LAYOUT") && !strcmp(getenv("PK_DIST_LAYOUT"), "wg256");
   if (n <= 4) launch_plain<4, 1>(a, st);
   else if (n <= 8) launch_plain<4, 2>(a, st);
   else if (n <= 12) launch_plain<4, 3>(a, st);
@@ -45,6 +62,7 @@ void launch_dist_fast12(const SolveArgs& a, hipStream_t st) {
   else if (n <= 20) launch_parked<4, 5>(a, st);
   else if (n <= 24) launch_parked<4, 6>(a, st);
   else if (n <= 28) launch_parked<4, 7>(a, st);
+  else if (n <= 32 && wg256) launch_nt<4, 8, true, 256>(a, st);
   else if (n <= 32) launch_parked<4, 8>(a, st);
   else if (n <= 40) launch_parked<8, 5>(a, st);
   else if (n <= 48) launch_parked<8, 6>(a, st);
