@@ -53,6 +53,7 @@ __host__ __device__ __forceinline__ int dist_metric_class(const SolveArgs& A) {
 template <bool CLIP, bool NORM, bool FLAT, bool SOL, int MC>
 struct DistFixed {
   static constexpr int SLOT_MC = MC;                 // which bookkeeping slots exist (Parked)
+  static constexpr bool LITERAL = false;             // the step loop's error norm is err_norm; a landing does not mask its idle rows
   __host__ __device__ static __forceinline__ bool clip(const SolveArgs&) { return CLIP; }
   __host__ __device__ static __forceinline__ bool normalize(const SolveArgs&) { return NORM; }
   __host__ __device__ static __forceinline__ bool flat(const SolveArgs&) { return FLAT; }
@@ -64,6 +65,10 @@ struct DistFixed {
 };
 struct DistAny {
   static constexpr int SLOT_MC = PK_DM_FULL;
+  // the run-time kernel keeps the literal forms -- the NaN-propagating maximum (group_max) in the step loop, idle rows masked to zero at
+  // a landing: slower, and what the specialised kernels are tested against (tests/test_gpu_dist_fast_variants.py on healthy replicas,
+  // tests/test_gpu_dist_fast_norm.py on replicas with non-finite parameters)
+  static constexpr bool LITERAL = true;
   __host__ __device__ static __forceinline__ bool clip(const SolveArgs& A) { return A.clip != 0; }
   __host__ __device__ static __forceinline__ bool normalize(const SolveArgs& A) { return A.normalize != 0; }
   __host__ __device__ static __forceinline__ bool flat(const SolveArgs& A) { return A.flat != nullptr; }
@@ -90,15 +95,21 @@ template <int RPL, int NT> struct Parked<RPL, false, NT> {
   __device__ __forceinline__ explicit Parked(double*) {}
   template <int K> __device__ __forceinline__ double get() const { return v[K]; }
   template <int K> __device__ __forceinline__ void set(double x) { v[K] = x; }
+  __device__ __forceinline__ void fence() {}
 };
 template <int RPL, int NT> struct Parked<RPL, true, NT> {
-  double* base;
-  __device__ __forceinline__ explicit Parked(double* lds) : base(lds + threadIdx.x) {}
+  typedef __attribute__((address_space(3))) double lds_double;
+  lds_double* base;
+  __device__ __forceinline__ explicit Parked(double* lds) : base((lds_double*)lds + threadIdx.x) {}
   template <int K> __device__ __forceinline__ double get() const { return base[K * NT]; }
   template <int K> __device__ __forceinline__ void set(double x) { base[K * NT] = x; }
+  // no instruction: the compiler forgets what it knows about the slots' contents, so a get() after it is a real LDS read and not a
+  // value it kept alive (or copied) in registers since the matching set()
+  __device__ __forceinline__ void fence() { asm volatile("" : "+v"(base)); }
 };
+// the parked layouts keep the site rows of the accepted state in RPL more slots (the step loop reads them at the top of a step, accepting lanes write them)
 template <int RPL, bool PARK, int NT = 256, class CFG = DistAny>
-constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)dist_fast_slots<RPL, CFG::SLOT_MC>() * NT * sizeof(double) : 0; }
+constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<RPL, CFG::SLOT_MC>() + RPL) * NT * sizeof(double) : 0; }
 
 // NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
 template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny>
@@ -106,10 +117,11 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   using Tab = ResolventTab<METHOD>;
   extern __shared__ __align__(16) double park_lds[];
   Parked<RPL, PARK, NT> pk(park_lds);
-  // slots: [0, RPL) S_i ; [RPL, 2 RPL) 1 + D_i ; then m1 (PK_DM_SUM), or previous site outputs, prevR, prevP, m1, m2, mdyn, shift (PK_DM_FULL)
+  // slots: [0, RPL) S_i ; [RPL, 2 RPL) 1 + D_i ; then m1 (PK_DM_SUM), or previous site outputs, prevR, prevP, m1, m2, mdyn, shift (PK_DM_FULL);
+  // PARK only: [K_Y, K_Y + RPL) the site rows of the last accepted state
   constexpr int MCS = CFG::SLOT_MC;
   constexpr int K_SR = 0, K_DG = RPL, K_PS = 2 * RPL, K_PR = 3 * RPL, K_PP = 3 * RPL + 1, K_M1 = (MCS == PK_DM_FULL ? 3 * RPL + 2 : 2 * RPL),
-                K_M2 = 3 * RPL + 3, K_MD = 3 * RPL + 4, K_SH = 3 * RPL + 5;
+                K_M2 = 3 * RPL + 3, K_MD = 3 * RPL + 4, K_SH = 3 * RPL + 5, K_Y = dist_fast_slots<RPL, MCS>();
   constexpr int RPB = NT / G;
   const int lane = lane_id();
   const int l = threadIdx.x & (G - 1);
@@ -145,6 +157,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     lsum += y.s[j];
   }
   y.sg = gsum<G>(lsum, lane);
+  if constexpr (PARK) static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(y.s[j]); });
 
   // ---- output / fused Morris metric (same semantics as Emitter in pk_solve_kernel.hpp)
   static_for<dist_fast_slots<RPL, MCS>() - 2 * RPL>([&](auto kc) { pk.template set<K_PS + decltype(kc)::value>(0.0); });
@@ -166,12 +179,17 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       if (CFG::sol(A)) { srow[-2] = vR; srow[-1] = vP; }
       if (CFG::flat(A)) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
     }
+    // An idle row (i >= n: rate 0, initial value 0) holds +0 or -0 in every accepted state -- each of its stage values is
+    // fma(0, x_P, +-0) with x_P finite -- so its clipped value is a zero already.  Adding a zero of either sign instead of +0.0 can
+    // change the row sum only from one zero to the other, and the running sum it is added to started from +0.0 and takes either zero
+    // to the same bits.  Only normalize (which would read y0 past its end) still needs the mask; the run-time kernel keeps it.
+    const bool masked = CFG::LITERAL || CFG::normalize(A);
     double vs[RPL];
     double loc = (l == 0) ? vR + vP : 0.0;
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
       const int i = l + G * j;
-      vs[j] = (i < n) ? val(v.s[j], 2 + i) : 0.0;
+      vs[j] = (i < n || !masked) ? val(v.s[j], 2 + i) : 0.0;
       if (i < n) {
         if (CFG::sol(A)) srow[G * j] = vs[j];
         if (CFG::flat(A)) fl[T5 + T + i * T + k] = vs[j];
@@ -240,13 +258,29 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 
   const double rtol = A.rtol, atol = A.atol;
   // max-norm helpers over the whole system (sites of this lane + shadows, then across the group)
-  auto group_max = [&](const Trk<RPL>& num, const Trk<RPL>& a, const Trk<RPL>& b) {
-    auto q = [&](double e, double ya, double yb) { return fabs(e) * approx_rcp(__builtin_fma(rtol, fmax(fabs(ya), fabs(yb)), atol)); };
+  auto q = [&](double e, double ya, double yb) { return fabs(e) * approx_rcp(__builtin_fma(rtol, fmax(fabs(ya), fabs(yb)), atol)); };
+  auto group_max = [&](const Trk<RPL>& num, const Trk<RPL>& a, const Trk<RPL>& b) {   // NaN-propagating: the initial step estimate; DistAny
     auto mx = [](double p, double r) { return (p > r || p != p) ? p : r; };
     double m = mx(q(num.R, a.R, b.R), q(num.P, a.P, b.P));
 #pragma unroll
     for (int j = 0; j < RPL; ++j) m = mx(m, q(num.s[j], a.s[j], b.s[j]));
     return gmax<G>(m, lane);
+  };
+  // The error norm of the step loop: the ratios of group_max for the error estimate e against the accepted state y and the candidate yn,
+  // their maximum with v_max_f64 (one instruction per element and per DPP level; it DROPS a NaN).  A NaN ratio (a NaN in a row's error or
+  // scale, inf * 0, 0 * inf) is found by unordered compares on pairs of ratios and turned into +inf, which v_max_f64 carries through the
+  // group; an inf ratio is the maximum anyway.  The loop treats +inf and NaN alike (reject, then the PK_ST_NONFINITE test), and for finite
+  // ratios the maximum has the bits group_max returns.
+  auto err_norm = [&](const Trk<RPL>& e, const Trk<RPL>& y, const Trk<RPL>& yn) {
+    double r[RPL + 2];
+    r[0] = q(e.R, y.R, yn.R); r[1] = q(e.P, y.P, yn.P);
+    static_for<RPL>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      r[2 + j] = q(e.s[j], y.s[j], yn.s[j]);
+    });
+    double m = tree_max(r);
+    if (any_nan(r)) m = __builtin_inf();
+    return gmax_num<G>(m, lane);
   };
   auto rhs_of = [&](const Trk<RPL>& Y) {            // f(Y); .sg unused
     Trk<RPL> f;
@@ -314,6 +348,12 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     const bool last = (tc + 1.0001 * h >= te);
     const double hs = last ? te - tc : ((tc + 2.0 * h > te) ? 0.5 * (te - tc) : h);
     if (over || !(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= over ? PK_ST_MAXSTEPS : PK_ST_HMIN; break; }
+    if constexpr (PARK) {
+      // the site rows of the state live in their slots between steps: read here (next to the rate slots, whose wait they share),
+      // written by the lanes that accept -- a rejecting lane has nothing to undo and an accepting one nothing to copy
+      pk.fence();
+      static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; y.s[j] = pk.template get<K_Y + j>(); });
+    }
     factor(Tab::GAM * hs);
 
     Trk<RPL> z = solve(trk_scale(hs, rhs_of(y)));
@@ -326,7 +366,21 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       if constexpr (kk == 1) u6 = trk_scale(Tab::E[1], z); else trk_axpy(u6, Tab::E[kk], z);
     });
 
-    const double err = group_max(u6, y, yn);
+    double err;
+    if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
+    // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
+    // a rejection too (acc = false), so the state is settled before the non-finite exit below looks at it
+    const bool acc = (err <= 1.0);
+    if constexpr (PARK) {
+      // accepting lanes record the candidate's site rows in their slots (LDS writes under the lane mask instead of a select per dword
+      // of the state); y.s is the candidate from here to the end of the iteration -- only a landing, which is an accept, reads it
+      if (acc) static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(yn.s[j]); });
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
+      y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; y.sg = acc ? yn.sg : y.sg;
+    } else {
+      if (acc) y = yn;
+    }
     if (err != err || err > 1e300) {
       ++nrej; after_reject = true; h = 0.1 * hs;
       const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
@@ -338,13 +392,10 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
     fac = fmax(1.0 / 6.0, fmin(5.0, fac));
     double hnew = hs * fast_rcp(fac);
-    // accept / reject / landing bookkeeping as selects on per-lane predicates: what a wave runs here does not depend on which of its
-    // replicas accept or land
-    const bool acc = (err <= 1.0), land = acc && last;
+    const bool land = acc && last;
     nacc += acc ? 1 : 0; nrej += acc ? 0 : 1;
     if (acc && after_reject) hnew = fmin(hnew, hs);
     after_reject = !acc;
-    if (acc) y = yn;
     tc = land ? te : (acc ? tc + hs : tc);
     h = (land && hs < h) ? fmax(hnew, h) : hnew;
     if (land) {

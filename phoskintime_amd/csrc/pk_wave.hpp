@@ -182,4 +182,34 @@ __device__ __forceinline__ double gmax(double v, int lane) {
   return v;
 }
 
+// ---- the plain maximum (one v_max_f64 per pair and per level): a NaN operand is DROPPED, +inf wins.  For callers that surface a NaN
+// themselves (the step loop of pk_dist_fast.hpp turns it into +inf before the reduction); finite values give the bits gmax gives.
+template <int LO, int HI, int N>
+__device__ __forceinline__ double tree_max_range(const double (&v)[N]) {
+  if constexpr (HI - LO == 1) return v[LO];
+  else { constexpr int MID = (LO + HI) / 2; return __builtin_fmax(tree_max_range<LO, MID>(v), tree_max_range<MID, HI>(v)); }
+}
+template <int N>
+__device__ __forceinline__ double tree_max(const double (&v)[N]) { return tree_max_range<0, N>(v); }
+// true when any element is a NaN: one unordered compare per PAIR of elements, the flags joined on the scalar unit
+template <int N>
+__device__ __forceinline__ bool any_nan(const double (&v)[N]) {
+  bool un = false;
+  static_for<(N + 1) / 2>([&](auto pc) {
+    constexpr int p = decltype(pc)::value;
+    un |= __builtin_isunordered(v[2 * p], v[2 * p + 1 < N ? 2 * p + 1 : 2 * p]);
+  });
+  return un;
+}
+template <int G>
+__device__ __forceinline__ double gmax_num(double v, int lane) {
+  if constexpr (G >= 2)  v = __builtin_fmax(v, partner<1>(v, lane));
+  if constexpr (G >= 4)  v = __builtin_fmax(v, partner<2>(v, lane));
+  if constexpr (G >= 8)  v = __builtin_fmax(v, partner<4>(v, lane));
+  if constexpr (G >= 16) v = __builtin_fmax(v, partner<8>(v, lane));
+  if constexpr (G >= 32) v = __builtin_fmax(v, partner<16>(v, lane));
+  if constexpr (G >= 64) v = __builtin_fmax(v, partner<32>(v, lane));
+  return v;
+}
+
 }  // namespace pk
