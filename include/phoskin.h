@@ -309,7 +309,14 @@ int      pk_network_objective_batch(pk_ctx*, pk_net*, pk_loss*, int64_t B, const
  * the trajectory Y [B,T,S] is written only if Y != NULL.  Results equal pk_network_simulate_batch followed by pk_network_objective_batch
  * up to the order of the sums.  Takes: topologies 0 / 4 on the default integrator (PK_METHOD_LRP12 = "default" or PK_METHOD_ARK436), loss
  * data whose three baselines are time index 0 and that observe no (state, time) twice.  Otherwise PK_ERR_UNSUPPORTED (the message says
- * which): call the two functions above instead.  x, y0, defaults, Y, status, n_steps, loss_sums, F: DEVICE pointers; t, lambdas: HOST. */
+ * which): call the two functions above instead.  x, y0, defaults, Y, status, n_steps, loss_sums, F: DEVICE pointers; t, lambdas: HOST.
+ * On request -- opts->method = PK_METHOD_ROS34PW2 or opts->kernel = PK_KERNEL_WORKSPACE -- the order-3 integrator scores the loss instead: all
+ * four topologies at every size, wherever pk_network_simulate_batch would run the general LDS kernel or the workspace kernel for these opts
+ * (opts->linsolve = PK_LINSOLVE_STRUCTURED forces the LDS kernel, as for simulate; a plan on the register-resident kernels answers
+ * PK_ERR_UNSUPPORTED).  It scores the observation lists bucketed by time index, so a (state, time) may be observed twice; the protein /
+ * phospho baselines must be time index 0 and no rna observation may precede the rna baseline.  A fused launch keeps N more doubles per
+ * candidate (the rna baseline): a larger LDS request, or past 160 KiB the workspace kernel with slabs N doubles longer than
+ * pk_network_workspace_bytes reports for plain launches.  Default opts answer exactly as before. */
 int      pk_network_simulate_objective_batch(pk_ctx*, pk_net*, pk_loss*, int64_t B, const double* x, int x_is_raw, const double* y0,
                                              int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, int loss_mode,
                                              const double* defaults, const double* lambdas, double fail_value, double* Y, int32_t* status,

@@ -16,6 +16,10 @@ hipError_t net_persistent_grid(const void* kernel, int threads, long long B, int
 // ROS34PW2-W with every per-candidate vector in an HBM workspace (net_solve_ws_kernel, pk_inst_net_ws.hip): no size limit
 hipError_t net_ws_grid(const NetDev& n, long long B, int* grid);
 hipError_t launch_net_ws(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
+// the same two kernels scoring the three-objective loss as they integrate (pk_inst_net_rosw_fused.hip)
+hipError_t net_ws_fused_grid(const NetDev& n, long long B, int* grid);
+hipError_t launch_net_ws_fused(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
+hipError_t launch_net_lds_fused(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
@@ -351,7 +355,9 @@ static NetPlan net_plan(const pk_net* n, const pk_solver_opts* opts) {
 
 int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { return n ? net_plan(n, opts).method : PK_ERR_ARG; }
 
-// `fused`: null, or the loss fields of NetSolveArgs filled in (pk_network_simulate_objective_batch); Y may then be null
+// `fused`: null, or the loss fields of NetSolveArgs filled in (pk_network_simulate_objective_batch); Y may then be null.  With
+// fused->loss_ptr set (the time-bucketed lists: the caller asked for the order-3 method or the workspace kernel) the launch runs where the
+// plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                              const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps,
                              const pk::NetSolveArgs* fused) {
@@ -362,8 +368,18 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   if (!x || !y0 || (!Y && !fused)) return pk_ctx_fail(c, PK_ERR_ARG, "null pointer");
   if (B > 0x7fffffffLL) return pk_ctx_fail(c, PK_ERR_ARG, "batch too large for one launch");
   if (n->d.model == 2 && n->max_sites > 16) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "combinatorial topology: <= 16 sites per protein");
-  const NetPlan plan = net_plan(n, opts_in);
+  NetPlan plan = net_plan(n, opts_in);
   if (plan.code != PK_OK) return pk_ctx_fail(c, plan.code, plan.refusal);
+  const bool rosw_fused = fused && fused->loss_ptr;
+  if (rosw_fused) {
+    if (plan.kernel == NetKernel::Reg || plan.kernel == NetKernel::CombReg)
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective with PK_METHOD_ROS34PW2: not on the register-resident kernels; ask for the general LDS "
+                                                "kernel (opts->linsolve = PK_LINSOLVE_STRUCTURED, kernel = \"lds\" in Python) or PK_KERNEL_WORKSPACE");
+    if (plan.kernel != NetKernel::Lds && plan.kernel != NetKernel::Workspace)
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective on request: PK_METHOD_ROS34PW2 on the LDS or the workspace kernel only");
+    // the rna baseline (N doubles) comes on top of the LDS of a plain launch: past 160 KiB the workspace kernel takes over
+    if (plan.kernel == NetKernel::Lds && pk::net_solve_fused_lds_bytes(n->d, n->nnzT) > 160 * 1024) plan.kernel = NetKernel::Workspace;
+  }
   const bool dp5 = plan.kernel == NetKernel::DP5;
   for (int k = 1; k < T; ++k) if (!(t_host[k] > t_host[k - 1])) return pk_ctx_fail(c, PK_ERR_ARG, "t must be strictly increasing");
   pk_solver_opts o;
@@ -397,7 +413,8 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
     a.loss_fail = fused->loss_fail; a.loss_sums = fused->loss_sums; a.loss_F = fused->loss_F; a.loss_rna_base = fused->loss_rna_base;
     for (int k = 0; k < 4; ++k) a.loss_lam[k] = fused->loss_lam[k];
     for (int k = 0; k < 3; ++k) a.loss_norm[k] = fused->loss_norm[k];
-    if (!(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
+    a.loss_ptr = fused->loss_ptr; a.loss_prot = fused->loss_prot; a.loss_site = fused->loss_site; a.loss_lobs = fused->loss_lobs; a.loss_lw = fused->loss_lw;
+    if (!rosw_fused && !(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
       return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: topologies 0 / 1 / 4 on the default additive integrator only; "
                                                 "use pk_network_simulate_batch + pk_network_objective_batch");
   }
@@ -428,13 +445,17 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   switch (plan.kernel) {
     case NetKernel::Workspace: {
       // ROS34PW2 on workspace slabs (net_solve_ws_kernel): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
-      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; } q{&n->d, &a, (long long)B, 0};
-      if (pk::net_ws_grid(n->d, (long long)B, &q.grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; bool fused; } q{&n->d, &a, (long long)B, 0, rosw_fused};
+      if ((rosw_fused ? pk::net_ws_fused_grid(n->d, (long long)B, &q.grid) : pk::net_ws_grid(n->d, (long long)B, &q.grid)) != hipSuccess)
+        return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
       auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
         const Q& r = *(const Q*)user;
-        return pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
+        return r.fused ? pk::launch_net_ws_fused(*r.d, *r.a, r.B, r.grid, (double*)scratch, s)
+                       : pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
       };
-      return pk_ctx_scratch_launch(c, (size_t)q.grid * pk::net_ws_slab_doubles(n->d) * sizeof(double), launch, &q);
+      // a fused launch's slab is N doubles longer (the rna baseline)
+      const size_t slab = rosw_fused ? pk::net_ws_fused_slab_doubles(n->d) : pk::net_ws_slab_doubles(n->d);
+      return pk_ctx_scratch_launch(c, (size_t)q.grid * slab * sizeof(double), launch, &q);
     }
     case NetKernel::DP5: {
       const size_t lb = pk::net_rk45_lds_bytes(n->d);
@@ -492,6 +513,11 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       // every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
       int threads = (n->d.S <= 128 && n->d.N <= 64) ? 64 : 256;        // measured at S = 500: 256 threads beat 128 by 1.33x
       if (const char* e = getenv("PK_NET_THREADS")) { const int v = atoi(e); if ((v == 64 || v == 128 || v == 256) && n->d.S <= 4 * v && n->d.N <= 2 * v) threads = v; }
+      if (rosw_fused) {
+        const hipError_t ef = pk::launch_net_lds_fused(n->d, a, (long long)B, threads, pk::net_solve_fused_lds_bytes(n->d, n->nnzT), stream);
+        if (ef != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(ef));
+        break;
+      }
       if (M == 0)      hipLaunchKernelGGL(pk::net_solve_kernel<0>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
       else if (M == 1) hipLaunchKernelGGL(pk::net_solve_kernel<1>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
       else if (M == 2) hipLaunchKernelGGL(pk::net_solve_kernel<2>, dim3((unsigned)B), dim3(threads), n->solve_lds_bytes, stream, n->d, a);
@@ -520,7 +546,12 @@ int pk_network_simulate_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, 
 // simulate + three-objective loss in ONE launch (SURVEY fused op (i), VERDICT r2 item 4 iii): the integrator scores the observations of the
 // loss handle at its output times; the trajectory is written only when Y != null.  Same F / loss_sums as pk_network_simulate_batch followed
 // by pk_network_objective_batch (up to the order of the sums).  PK_ERR_UNSUPPORTED when the network / options / loss data do not take the path.
+// By default that path is the dense-lane additive kernel (topologies 0 / 1 / 4).  On request -- opts->method = PK_METHOD_ROS34PW2 or
+// opts->kernel = PK_KERNEL_WORKSPACE -- the order-3 LDS / workspace kernels score the loss handle's time-bucketed lists: every topology,
+// every size, duplicate observations allowed.
 int pk_loss_fused_tables(const pk_loss* l, const double** obs, const double** w, double* norms, int* T, int* rna_base);
+int pk_loss_fused_lists(const pk_loss* l, const int32_t** ptr, const int32_t** prot, const int32_t** site, const double** obs, const double** w,
+                        double* norms, int* T, int* rna_base);
 int pk_network_simulate_objective_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_t B, const double* x, int x_is_raw, const double* y0,
                                         int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, int loss_mode,
                                         const double* defaults, const double* lambdas, double fail_value, double* Y, int32_t* status,
@@ -533,7 +564,11 @@ int pk_network_simulate_objective_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_
   pk::NetSolveArgs f;
   std::memset(&f, 0, sizeof(f));
   int Tl = 0;
-  if (!pk_loss_fused_tables(l, &f.loss_obs, &f.loss_w, f.loss_norm, &Tl, &f.loss_rna_base))
+  if (opts && (opts->method == PK_METHOD_ROS34PW2 || opts->kernel == PK_KERNEL_WORKSPACE)) {
+    if (!pk_loss_fused_lists(l, &f.loss_ptr, &f.loss_prot, &f.loss_site, &f.loss_lobs, &f.loss_lw, f.loss_norm, &Tl, &f.loss_rna_base))
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: protein / phospho baselines must be time index 0 and rna observations not earlier "
+                                                "than the rna baseline");
+  } else if (!pk_loss_fused_tables(l, &f.loss_obs, &f.loss_w, f.loss_norm, &Tl, &f.loss_rna_base))
     return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: protein / phospho baselines must be time index 0, rna observations not earlier than "
                                               "the rna baseline, and no (state, time) observed twice");
   if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the loss data were created for");

@@ -190,6 +190,10 @@ struct pk_loss {
   // a protein / phospho baseline other than time index 0, an rna observation before the rna baseline (the reference's production data:
   // baselines at t = 0, 4, 0 and rna observed from t = 4 on, runner.py:545-547), or two observations of one (state, time).
   const double* dense_obs = nullptr; const double* dense_w = nullptr;
+  // the same observations bucketed by time index (a CSR over t per modality, NetSolveArgs::loss_ptr ...): what the order-3 kernels score at
+  // each output row.  Any topology, and a (state, time) may be observed twice; null under the two baseline conditions above
+  const int32_t* lc_ptr = nullptr; const int32_t* lc_prot = nullptr; const int32_t* lc_site = nullptr;
+  const double* lc_obs = nullptr; const double* lc_w = nullptr;
 };
 
 namespace {
@@ -258,8 +262,44 @@ pk_loss* pk_network_loss_create(pk_ctx* c, pk_net* net, const pk_loss_data* d, i
       if (!dup) { l->dense_obs = up(l, ob.data(), ob.size(), ok); l->dense_w = up(l, wt.data(), wt.size(), ok); }
     }
   }
+  if (ok && d->prot_base_idx == 0 && d->pho_base_idx == 0 && rna_after_base) {
+    // stable counting sort of each modality by time index into one set of arrays (protein | rna | phospho)
+    const size_t tot = (size_t)d->n_prot + d->n_rna + d->n_pho, T1 = (size_t)T + 1;
+    std::vector<int32_t> ptr(3 * T1, 0), pr(tot, 0), si(tot, 0);
+    std::vector<double> ob(tot, 0.0), wt(tot, 0.0);
+    const int cnt[3] = {d->n_prot, d->n_rna, d->n_pho};
+    const int32_t* tt[3] = {d->t_prot, d->t_rna, d->t_pho};
+    const int32_t* pp[3] = {d->p_prot, d->p_rna, d->p_pho};
+    const double* oo[3] = {d->obs_prot, d->obs_rna, d->obs_pho};
+    const double* ww[3] = {d->w_prot, d->w_rna, d->w_pho};
+    size_t first = 0;
+    for (int m = 0; m < 3; ++m) {
+      int32_t* pm = ptr.data() + m * T1;
+      for (int k = 0; k < cnt[m]; ++k) ++pm[tt[m][k] + 1];
+      pm[0] = (int32_t)first;
+      for (int t = 0; t < T; ++t) pm[t + 1] += pm[t];
+      std::vector<int32_t> fill(pm, pm + T);
+      for (int k = 0; k < cnt[m]; ++k) {
+        const int at = fill[tt[m][k]]++;
+        pr[at] = pp[m][k]; si[at] = (m == 2) ? d->s_pho[k] : 0; ob[at] = oo[m][k]; wt[at] = ww[m][k];
+      }
+      first += (size_t)cnt[m];
+    }
+    l->lc_ptr = up(l, ptr.data(), ptr.size(), ok); l->lc_prot = up(l, pr.data(), tot, ok); l->lc_site = up(l, si.data(), tot, ok);
+    l->lc_obs = up(l, ob.data(), tot, ok); l->lc_w = up(l, wt.data(), tot, ok);
+  }
   if (!ok) { pk_ctx_fail(c, PK_ERR_NOMEM, "hipMalloc / hipMemcpy failed"); pk_network_loss_destroy(l); return nullptr; }
   return l;
+}
+
+// for the fused launch of the order-3 kernels (pk_network.hip): the time-bucketed lists, the normalisations, the grid length and the rna
+// baseline row; 0 when the lists cannot be fused (a protein / phospho baseline other than time index 0, an rna observation before its baseline)
+int pk_loss_fused_lists(const pk_loss* l, const int32_t** ptr, const int32_t** prot, const int32_t** site, const double** obs, const double** w,
+                        double* norms, int* T, int* rna_base) {
+  if (!l || !l->lc_ptr) return 0;
+  *ptr = l->lc_ptr; *prot = l->lc_prot; *site = l->lc_site; *obs = l->lc_obs; *w = l->lc_w;
+  norms[0] = l->d.norm_p; norms[1] = l->d.norm_r; norms[2] = l->d.norm_ph; *T = l->T; *rna_base = l->d.base_rna;
+  return 1;
 }
 
 // for the fused launch (pk_network.hip): the dense tables, the normalisations and the grid length; 0 when the lists cannot be fused

@@ -51,6 +51,10 @@ struct NetSolveArgs {
   const double* loss_obs; const double* loss_w; const double* loss_defaults;
   double loss_lam[4], loss_norm[3], loss_fail; int loss_mode, loss_rna_base;
   double* loss_sums; double* loss_F;
+  // fused objective of the order-3 kernels (net_rosw_solve<.., FUSED = true>): the loss handle's observation lists bucketed by time index
+  // instead of the dense tables.  One set of arrays (protein | rna | phospho, each sorted by time index); modality m's observations of
+  // output row t are entries loss_ptr[m (T + 1) + t] .. loss_ptr[m (T + 1) + t + 1].  loss_site: phospho entries only
+  const int32_t* loss_ptr; const int32_t* loss_prot; const int32_t* loss_site; const double* loss_lobs; const double* loss_lw;
 };
 
 // block-wide NaN-propagating max; `red` holds >= 17 doubles of LDS
@@ -155,9 +159,16 @@ struct NetWsLayout {
 
 // ROS34PW2-W of candidate b, from loading x and y0 to the status / n_steps write.  L: the candidate's NetLds; base: its stage vectors
 // (net_rosw_doubles - NetLds::doubles of them); red: >= 24 doubles of LDS for the reductions.
-template <int MODEL, class Layout>
+//
+// FUSED: the candidate is scored as it integrates (pk_network_simulate_objective_batch on request of the order-3 method): at the initial
+// row and after every landing that fills an output row, the observations of that time index (A.loss_ptr ...) are scored from y -- what
+// net_objective_kernel (pk_network_loss.hip) computes from a stored trajectory, into three per-thread partial sums.  Baselines: y0 for
+// protein / phospho (time index 0); the mRNA values at output row A.loss_rna_base, kept in rbase (N doubles) from the landing that
+// produces them (no rna observation is earlier: the host checks).  The trajectory is written only if A.Y != null.  The plain
+// instantiation has none of this: its A.Y is never null and rbase is unused.
+template <int MODEL, bool FUSED, class Layout>
 __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveArgs& A, const Layout& lay, const long long b, NetLds L,
-                                               double* const base, double* const red) {
+                                               double* const base, double* const red, double* const rbase = nullptr) {
   using namespace rosw;
   constexpr int model = MODEL;
   const int S = n.S, N = n.N;
@@ -181,9 +192,51 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
   const double* xb = A.x + b * n.n_var;
   for (int k = tid; k < n.n_var; k += nt) L.p[k] = A.x_is_raw ? softplus(xb[k]) : xb[k];
   const double* y0 = A.y0 + (A.y0_batched ? b * S : 0);
-  double* Yout = A.Y + b * (size_t)A.T * S;
-  for (int k = tid; k < S; k += nt) { const double v = y0[k]; y[k] = v; Yout[k] = v; }
+  const bool wY = !FUSED || A.Y != nullptr;
+  double* Yout = wY ? A.Y + b * (size_t)A.T * S : nullptr;
+  for (int k = tid; k < S; k += nt) { const double v = y0[k]; y[k] = v; if (wY) Yout[k] = v; }
   __syncthreads();
+
+  // ---- fused objective: score output row `row`, which y holds (a barrier lies behind its last write, and none of y changes before the
+  // next one).  Partial sums and the non-finite flag are per thread and per candidate
+  double lacc[3] = {0.0, 0.0, 0.0};
+  bool ybad = false;
+  auto score_row = [&](const int row) {
+    if constexpr (FUSED) {
+      for (int k = tid; k < S; k += nt) if (nonfinite(y[k])) ybad = true;          // np.all(np.isfinite(Y)) of the reference (optproblem.py:130)
+      if (row == A.loss_rna_base) {
+        for (int i = tid; i < N; i += nt) rbase[i] = y[n.offset_y[i]];
+        __syncthreads();
+      }
+      const int32_t* ptr = A.loss_ptr + row;
+      const int T1 = A.T + 1;
+      for (int k = ptr[0] + tid; k < ptr[1]; k += nt) {                            // protein: P plus all sites / all 2^ns states
+        const int i = A.loss_prot[k], st = n.offset_y[i];
+        const int cnt = (model == 2) ? (1 << n.n_sites[i]) : 1 + n.n_sites[i];
+        double tt = 0.0, tb = 0.0;
+        for (int m = 0; m < cnt; ++m) { tt += y[st + 1 + m]; tb += y0[st + 1 + m]; }
+        const double obs = A.loss_lobs[k], pred = fold_change(tt, tb);
+        lacc[0] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+      }
+      for (int k = ptr[T1] + tid; k < ptr[T1 + 1]; k += nt) {                      // rna: the mRNA row against the kept baseline
+        const int i = A.loss_prot[k];
+        const double obs = A.loss_lobs[k], pred = fold_change(y[n.offset_y[i]], rbase[i]);
+        lacc[1] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+      }
+      for (int k = ptr[2 * T1] + tid; k < ptr[2 * T1 + 1]; k += nt) {              // phospho: site row / all masks with the site's bit
+        const int i = A.loss_prot[k], st = n.offset_y[i], j = A.loss_site[k];
+        double a, c;
+        if (model == 2) {
+          a = 0.0; c = 0.0;
+          const int cnt = 1 << n.n_sites[i];
+          for (int m = 0; m < cnt; ++m) if (m & (1 << j)) { a += y[st + 1 + m]; c += y0[st + 1 + m]; }
+        } else { a = y[st + 2 + j]; c = y0[st + 2 + j]; }
+        const double obs = A.loss_lobs[k], pred = fold_change(a, c);
+        lacc[2] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+      }
+    }
+  };
+  score_row(0);
 
   // ---- block factorisation of  g I - J_blockdiag(y)  and block solve  x <- W^{-1} r  (in place: r -> x), one thread per protein
   auto factor = [&](const double g) {
@@ -379,11 +432,14 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
     }
     if (status != PK_ST_OK) break;
     const int row = stop_out[si];
-    if (row >= 0) for (int k = tid; k < S; k += nt) Yout[(size_t)row * S + k] = y[k];
+    if (row >= 0) {
+      if (wY) for (int k = tid; k < S; k += nt) Yout[(size_t)row * S + k] = y[k];
+      score_row(row);
+    }
     const int jn = net_bucket(tc, n.kin_grid, n.n_grid);
     if (jn != jb) { jb = jn; net_prepare_bucket(n, L, jb); }
   }
-  if (status != PK_ST_OK) {
+  if (status != PK_ST_OK && wY) {
     // flagged candidate: every output row that was not reached is NaN (never garbage)
     const double qnan = __builtin_nan("");
     for (int si = 0; si < A.n_stops; ++si) {
@@ -395,10 +451,37 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
     if (A.status) A.status[b] = status;
     if (A.n_steps) { A.n_steps[2 * b] = nacc; A.n_steps[2 * b + 1] = nrej; }
   }
+  if constexpr (FUSED) {
+    // objective assembly of GlobalODE_MOO._evaluate (optproblem.py:99-160), as net_objective_kernel does it from a stored trajectory
+    const double lp = block_sum(lacc[0], red), lr = block_sum(lacc[1], red), lph = block_sum(lacc[2], red);
+    double prior = 0.0;
+    if (A.loss_defaults) {
+      double acc = 0.0;
+      for (int k = tid; k < 5 * N; k += nt) {
+        const int grp = k / N, i = k - grp * N;
+        const int off = (grp == 0 ? sl.A : grp == 1 ? sl.B : grp == 2 ? sl.C : grp == 3 ? sl.D : sl.E) + i;
+        const double d = (L.p[off] - A.loss_defaults[off]) / (A.loss_defaults[off] + 1e-6);
+        acc = __builtin_fma(d, d, acc);
+      }
+      prior = A.loss_lam[3] * (block_sum(acc, red) / (double)(5 * N));
+    }
+    const bool bad = block_max(ybad ? 1.0 : 0.0, red) != 0.0 || status != PK_ST_OK;
+    if (tid == 0) {
+      if (A.loss_sums) { A.loss_sums[3 * b] = lp; A.loss_sums[3 * b + 1] = lr; A.loss_sums[3 * b + 2] = lph; }
+      if (A.loss_F) {
+        A.loss_F[3 * b] = bad ? A.loss_fail : (lp * A.loss_norm[0]) * A.loss_lam[0] + prior;
+        A.loss_F[3 * b + 1] = bad ? A.loss_fail : (lr * A.loss_norm[1]) * A.loss_lam[1] + prior;
+        A.loss_F[3 * b + 2] = bad ? A.loss_fail : (lph * A.loss_norm[2]) * A.loss_lam[2] + prior;
+      }
+    }
+  }
 }
 
-// One workgroup per candidate, everything in dynamic LDS: the work area, 24 doubles of reductions, then the TF CSR
-template <int MODEL>
+__host__ __device__ inline size_t net_solve_lds_bytes(const NetDev& n, int nnzT);
+
+// One workgroup per candidate, everything in dynamic LDS: the work area, 24 doubles of reductions, then the TF CSR (FUSED: then the
+// rna baseline, N doubles)
+template <int MODEL, bool FUSED = false>
 __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const NetSolveArgs A) {
   extern __shared__ __align__(16) double lds[];
   const int N = n.N, nnzT = n.TF_indptr[N];
@@ -412,7 +495,8 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
   for (int k = tid; k <= N; k += nt) tf_ptr[k] = n.TF_indptr[k];
   for (int k = tid; k < N; k += nt) tf_deg[k] = n.tf_deg[k];
   const NetRegLayout lay(n, tf_dat, tf_deg, tf_ptr, tf_idx);
-  net_rosw_solve<MODEL>(n, A, lay, blockIdx.x, NetLds(lds, n), lds + NetLds::doubles(n), red);
+  net_rosw_solve<MODEL, FUSED>(n, A, lay, blockIdx.x, NetLds(lds, n), lds + NetLds::doubles(n), red,
+                               FUSED ? lds + net_solve_lds_bytes(n, nnzT) / 8 : nullptr);
 }
 
 // Networks of any size: every per-candidate vector in a slab of an HBM workspace instead of LDS, so nothing limits S or N but device
@@ -428,15 +512,32 @@ __global__ __launch_bounds__(256) void net_solve_ws_kernel(const NetDev n, const
   const NetWsLayout lay(n);
   for (long long b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();                                   // the previous candidate of this workgroup is done with the slab
-    net_rosw_solve<MODEL>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red);
+    net_rosw_solve<MODEL, false>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red);
+  }
+}
+
+// The same persistent grid scoring the loss (net_rosw_solve<MODEL, true>); the slab is N doubles longer: the rna baseline, behind the work
+// area.  A kernel of its own so that the plain one keeps its attributes: scoring costs 15 VGPRs (134-136), one workgroup per CU less than
+// the plain kernel's four; held to 128 here (12-20 B of scratch per lane) the resident grid stays 1 024
+template <int MODEL>
+__global__ __launch_bounds__(256, 4) void net_solve_ws_fused_kernel(const NetDev n, const NetSolveArgs A, const long long B, double* __restrict__ ws,
+                                                                    const size_t slab) {
+  __shared__ double red[24];
+  double* const base0 = ws + (size_t)blockIdx.x * slab;
+  const NetWsLayout lay(n);
+  for (long long b = blockIdx.x; b < B; b += gridDim.x) {
+    __syncthreads();                                   // the previous candidate of this workgroup is done with the slab (rna baseline included)
+    net_rosw_solve<MODEL, true>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red, base0 + net_rosw_doubles(n));
   }
 }
 
 __host__ __device__ inline size_t net_ws_slab_doubles(const NetDev& n) { return (net_rosw_doubles(n) + 15) / 16 * 16; }
+__host__ __device__ inline size_t net_ws_fused_slab_doubles(const NetDev& n) { return (net_rosw_doubles(n) + n.N + 15) / 16 * 16; }
 __device__ __host__ inline size_t net_solve_lds_doubles(const NetDev& n) { return net_rosw_doubles(n) + 24; }
 // + the LDS copy of the TF CSR: nnz doubles + N doubles + (N + 1 + nnz) int32 (rounded up to doubles)
-__host__ inline size_t net_solve_lds_bytes(const NetDev& n, int nnzT) {
+__host__ __device__ inline size_t net_solve_lds_bytes(const NetDev& n, int nnzT) {
   return (net_solve_lds_doubles(n) + (size_t)nnzT + n.N) * 8 + (((size_t)n.N + 1 + nnzT) * 4 + 7) / 8 * 8;
 }
+__host__ inline size_t net_solve_fused_lds_bytes(const NetDev& n, int nnzT) { return net_solve_lds_bytes(n, nnzT) + (size_t)n.N * 8; }
 
 }  // namespace pk

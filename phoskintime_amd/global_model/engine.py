@@ -194,11 +194,19 @@ class NetworkEngine:
 
     def simulate_objective_batch(self, loss, x, t_eval, y0=None, raw: bool = False, rtol: float = 1e-8, atol: float = 1e-8, max_steps: int = 1000000,
                                  err_norm: str = "max", loss_mode: int = 0, defaults=None, lambdas=(1.0, 1.0, 1.0, 0.0), fail_value: float = 1e12,
-                                 want_Y: bool = False):
+                                 want_Y: bool = False, method: str = "auto", kernel: str = "auto"):
         """simulate_odeint -> LOSS_FN -> objectives (optproblem.py:99-160) for B candidates in ONE launch: the integrator scores the
-        observations at its output times, the trajectory stays in registers (``want_Y``: also written).  Returns
+        observations at its output times, the trajectory never reaches HBM (``want_Y``: also written).  Returns
         (loss_sums [B, 3], F [B, 3], status [B], n_steps [B, 2], Y or None), or ``None`` when this network / loss data do not take the fused
-        path (``pk_network_simulate_objective_batch`` answers PK_ERR_UNSUPPORTED: call ``simulate_batch`` + ``objective_batch``)."""
+        path (``pk_network_simulate_objective_batch`` answers PK_ERR_UNSUPPORTED: call ``simulate_batch`` + ``objective_batch``).
+        ``method`` / ``kernel`` as in ``simulate_batch``.  By default the fused launch is the dense-lane order-4 kernel (topologies
+        0 / 1 / 4, <= 512 lanes).  ``method="rosw"`` or ``kernel="workspace"`` asks the order-3 method to score the loss: every topology
+        at every size, on the general LDS kernel or the HBM-workspace kernel (``None`` where the plan is a register-resident kernel:
+        ask for ``kernel="lds"``); a (state, time) may then be observed twice."""
+        if method not in ("auto", "ark", "rosw", "dp5"):
+            raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
+        if kernel not in ("auto", "lds", "workspace"):
+            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
         dev = torch.device("cuda", self.ctx.device)
         xd = _dev_f64(x, dev)
         if xd.dim() == 1:
@@ -222,7 +230,7 @@ class NetworkEngine:
         sums = torch.empty((B, 3), dtype=torch.float64, device=dev)
         F = torch.empty((B, 3), dtype=torch.float64, device=dev)
         lam = (C.c_double * 4)(*[float(v) for v in lambdas])
-        opts = _capi.default_opts(rtol=rtol, atol=atol, max_steps=max_steps, err_norm=err_norm)
+        opts = self._opts(method, kernel, rtol=rtol, atol=atol, max_steps=max_steps, err_norm=err_norm)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         rc = self.ctx.lib.pk_network_simulate_objective_batch(self.ctx.handle, self._h, loss, B, _ptr(xd), int(raw), _ptr(yd), yb, th.ctypes.data, T,
                                                               C.byref(opts), int(loss_mode), _ptr(dd), C.cast(lam, C.c_void_p), float(fail_value),

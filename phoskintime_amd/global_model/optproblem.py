@@ -38,17 +38,26 @@ class GlobalODEBatch:
         # combinatorial populations (tests/test_gpu_network.py) -- opt-in only
         self.err_norm = err_norm
         self.fused = None          # None: not asked yet; True / False: whether the library runs simulate + objective as one launch here
+        self._fused_method = "auto"                            # the method the accepted fused launch was asked with
         self.xl, self.xu = xl, xu
         self.n_var, self.n_obj = eng.n_var, 3
 
     def evaluate_device(self, X) -> torch.Tensor:
         """X [b, n_var] raw (softplus space, params.py:106-132; numpy or a GPU tensor) -> F [b, 3] as a GPU tensor, nothing returns to the
-        host.  ONE launch where the integrator can score the observations itself (arrow topologies on the default integrator: no
-        trajectory in HBM), else one simulate launch + one loss launch."""
+        host.  ONE launch where the integrator can score the observations itself -- arrow topologies on the default integrator, and every
+        network whose default integrator is the order-3 method on the general LDS or the HBM-workspace kernel (the combinatorial topology
+        beyond 3 sites, everything beyond one workgroup's LDS): no trajectory in HBM -- else one simulate launch + one loss launch."""
         if self.fused is not False:
-            out = self.eng.simulate_objective_batch(self.loss, X, self.time_grid, y0=self.y0, raw=True, rtol=self.rtol, atol=self.atol,
-                                                    max_steps=self.max_steps * self.time_grid.size, err_norm=self.err_norm, loss_mode=self.loss_mode,
-                                                    defaults=self.defaults, lambdas=self.lam, fail_value=self.fail_value)
+            ask = lambda method: self.eng.simulate_objective_batch(
+                self.loss, X, self.time_grid, y0=self.y0, raw=True, rtol=self.rtol, atol=self.atol, max_steps=self.max_steps * self.time_grid.size,
+                err_norm=self.err_norm, loss_mode=self.loss_mode, defaults=self.defaults, lambdas=self.lam, fail_value=self.fail_value, method=method)
+            out = ask(self._fused_method)
+            if out is None and self.fused is None and self.eng.resolved_method() == "rosw":
+                # the two-launch path below would integrate with the order-3 method: the library fuses exactly where that runs the LDS or
+                # the workspace kernel (the same integrator, the same steps, the same F)
+                out = ask("rosw")
+                if out is not None:
+                    self._fused_method = "rosw"
             self.fused = out is not None                        # the library's answer for this network / loss data: asked once
             if out is not None:
                 return out[1]
