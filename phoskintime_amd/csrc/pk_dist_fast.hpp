@@ -117,6 +117,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   using Tab = ResolventTab<METHOD>;
   extern __shared__ __align__(16) double park_lds[];
   Parked<RPL, PARK, NT> pk(park_lds);
+  // the parked slots of every wave the launch bounds promise a CU (4 SIMDs x MINB) must fit its 160 KiB; the tightest entry of the launch
+  // tables is DistAny at 8 rows: 38 slots x 512 B x 8 waves = 152 KiB, so three more slots per thread would not fit there
+  static_assert(dist_fast_lds_bytes<RPL, PARK, 64, CFG>() * 4 * MINB <= 160 * 1024, "parked slots exceed the CU's LDS at this occupancy");
   // slots: [0, RPL) S_i ; [RPL, 2 RPL) 1 + D_i ; then m1 (PK_DM_SUM), or previous site outputs, prevR, prevP, m1, m2, mdyn, shift (PK_DM_FULL);
   // PARK only: [K_Y, K_Y + RPL) the site rows of the last accepted state
   constexpr int MCS = CFG::SLOT_MC;
@@ -168,13 +171,32 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   auto emit = [&](const int k, const Trk<RPL>& v, auto nf) {
     constexpr bool nan_fill = decltype(nf)::value;
     double* fl = CFG::flat(A) ? A.flat + rep * A.F : nullptr;
+    // The clip `x < 0 ? 0 : x` (a compare and two selects per double) changes a value only where its sign bit is set: x < 0 is false for
+    // every x with a clear sign bit, +0 and a positive NaN included.  The specialised kernels therefore OR the high dwords of the row's
+    // values (two idle-row zeros of either sign included: a -0 only sends the wave down the literal path) and run the literal clip only
+    // when some lane of the wave has a sign bit set -- a branch on the scalar unit, uniform over the wave.  Same bits on both paths.
+    bool clip_now = CFG::clip(A);
+    if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
+      typedef int dwords __attribute__((ext_vector_type(2)));      // element 1 = the high dword; as a shift of the 64 bits the OR is done on both dwords
+      int sgn = __builtin_bit_cast(dwords, v.R).y | __builtin_bit_cast(dwords, v.P).y;
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) sgn |= __builtin_bit_cast(dwords, v.s[j]).y;
+      clip_now = __builtin_amdgcn_ballot_w64(sgn < 0) != 0;
+    }
     auto val = [&](double x, int state) {
       if (nan_fill) return __builtin_nan("");
-      double r = CFG::clip(A) ? ((x < 0.0) ? 0.0 : x) : x;
+      double r = (CFG::LITERAL && CFG::clip(A)) ? ((x < 0.0) ? 0.0 : x) : x;          // the run-time kernel clips value by value
       if (CFG::normalize(A)) r *= 1.0 / y0p[state];
       return r;
     };
-    const double vR = val(v.R, 0), vP = val(v.P, 1);
+    Trk<RPL> c = v;                                     // the clipped state
+    if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
+      asm volatile("" : "+v"(c.R));                     // keeps this a branch: without it the compiler folds the test into each select
+      c.R = (c.R < 0.0) ? 0.0 : c.R; c.P = (c.P < 0.0) ? 0.0 : c.P;
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) c.s[j] = (c.s[j] < 0.0) ? 0.0 : c.s[j];
+    }
+    const double vR = val(c.R, 0), vP = val(c.P, 1);
     if (l == 0) {
       if (CFG::sol(A)) { srow[-2] = vR; srow[-1] = vP; }
       if (CFG::flat(A)) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
@@ -189,7 +211,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
       const int i = l + G * j;
-      vs[j] = (i < n || !masked) ? val(v.s[j], 2 + i) : 0.0;
+      vs[j] = (i < n || !masked) ? val(c.s[j], 2 + i) : 0.0;
       if (i < n) {
         if (CFG::sol(A)) srow[G * j] = vs[j];
         if (CFG::flat(A)) fl[T5 + T + i * T + k] = vs[j];
@@ -253,7 +275,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   };
 
   emit(0, y, std::false_type{});
-  int status = PK_ST_OK, nacc = 0, nrej = 0;
+  int status = PK_ST_OK, nacc = 0;
   if (T < 2) { finish(status, 0, 0); return; }
 
   const double rtol = A.rtol, atol = A.atol;
@@ -338,79 +360,113 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // resolvent-form step (the right-hand side is affine): z_1 = M^{-1} h f(y), z_{k+1} = M^{-1} z_k,
   //   y_new = y + sum_k B_k z_k ,  err = sum_k E_k z_k     (ResolventTab: RODAS4, LRP8 or LRP12)
   bool after_reject = false;
+  // nacc counts the accepted steps.  nsec counts the rejected ones in the run-time kernel and ALL steps in the specialised kernels (one
+  // increment per step whatever its fate, and the budget test reads it without an add; finish() gets the difference -- integer, exact)
+  int nsec = 0;
   // vmcnt(0) alone: every load of the prologue has landed before the loop, so the loop's own wait is the one for tnx at a landing and
   // no step waits for the stores of the landing before it
   __builtin_amdgcn_s_waitcnt(0x0F70);
+  // The outer loop runs once on a healthy replica.  In the specialised kernels a step whose error is NaN or inf leaves the step loop on a
+  // flag; what the run-time kernel decides inside its loop (PK_ST_NONFINITE, or carry on with a tenth of the step) is decided below the
+  // step loop, on values that rejected step did not change, and a replica that carries on re-enters the step loop.  A replica's lanes
+  // move together, and no other replica's values are read, so every replica takes the steps it took.
   while (true) {
-    const double tnx = A.t[k + 1 < T ? k + 1 : T - 1];   // the output time after te, fetched a whole step before a landing can need it
-    // failure exits (step budget, vanishing step): status is set here and the NaN rows are written after the loop
-    const bool over = nacc + nrej >= A.max_steps;
-    const bool last = (tc + 1.0001 * h >= te);
-    const double hs = last ? te - tc : ((tc + 2.0 * h > te) ? 0.5 * (te - tc) : h);
-    if (over || !(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= over ? PK_ST_MAXSTEPS : PK_ST_HMIN; break; }
-    if constexpr (PARK) {
-      // the site rows of the state live in their slots between steps: read here (next to the rate slots, whose wait they share),
-      // written by the lanes that accept -- a rejecting lane has nothing to undo and an accepting one nothing to copy
-      pk.fence();
-      static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; y.s[j] = pk.template get<K_Y + j>(); });
-    }
-    factor(Tab::GAM * hs);
-
-    Trk<RPL> z = solve(trk_scale(hs, rhs_of(y)));
-    Trk<RPL> yn = y; trk_axpy(yn, Tab::B[0], z);
-    Trk<RPL> u6;
-    static_for<Tab::NS - 1>([&](auto kc) {
-      constexpr int kk = 1 + decltype(kc)::value;
-      z = solve(z);
-      trk_axpy(yn, Tab::B[kk], z);
-      if constexpr (kk == 1) u6 = trk_scale(Tab::E[1], z); else trk_axpy(u6, Tab::E[kk], z);
-    });
-
-    double err;
-    if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
-    // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
-    // a rejection too (acc = false), so the state is settled before the non-finite exit below looks at it
-    const bool acc = (err <= 1.0);
-    if constexpr (PARK) {
-      // accepting lanes record the candidate's site rows in their slots (LDS writes under the lane mask instead of a select per dword
-      // of the state); y.s is the candidate from here to the end of the iteration -- only a landing, which is an accept, reads it
-      if (acc) static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(yn.s[j]); });
-#pragma unroll
-      for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
-      y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; y.sg = acc ? yn.sg : y.sg;
-    } else {
-      if (acc) y = yn;
-    }
-    if (err != err || err > 1e300) {
-      ++nrej; after_reject = true; h = 0.1 * hs;
-      const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
-      if (bad != 0.0 || (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC)) || (nonfinite(Dsum)) || (nonfinite(Scw))) {
-        status |= PK_ST_NONFINITE; break;
+    bool nonfin = false;
+    while (true) {
+      const double tnx = A.t[k + 1 < T ? k + 1 : T - 1];   // the output time after te, fetched a whole step before a landing can need it
+      // failure exits (step budget, vanishing step): status is set here and the NaN rows are written after the loop
+      const bool over = (CFG::LITERAL ? nacc + nsec : nsec) >= A.max_steps;
+      const bool last = (tc + 1.0001 * h >= te);
+      const double hs = last ? te - tc : ((tc + 2.0 * h > te) ? 0.5 * (te - tc) : h);
+      if (over || !(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= over ? PK_ST_MAXSTEPS : PK_ST_HMIN; break; }
+      if constexpr (PARK) {
+        // the site rows of the state live in their slots between steps: read here (next to the rate slots, whose wait they share),
+        // written by the lanes that accept -- a rejecting lane has nothing to undo and an accepting one nothing to copy
+        pk.fence();
+        static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; y.s[j] = pk.template get<K_Y + j>(); });
       }
-      continue;
-    }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
-    double hnew = hs * fast_rcp(fac);
-    const bool land = acc && last;
-    nacc += acc ? 1 : 0; nrej += acc ? 0 : 1;
-    if (acc && after_reject) hnew = fmin(hnew, hs);
-    after_reject = !acc;
-    tc = land ? te : (acc ? tc + hs : tc);
-    h = (land && hs < h) ? fmax(hnew, h) : hnew;
-    if (land) {
-      te = tnx;
-      asm volatile("" : "+v"(te));                      // pins this copy ahead of the row's stores: its wait then covers the load of tnx alone
-      // re-sum the sites at every landing so the tracked sum cannot drift
-      double loc = 0.0;
+      factor(Tab::GAM * hs);
+
+      Trk<RPL> z = solve(trk_scale(hs, rhs_of(y)));
+      Trk<RPL> yn = y; trk_axpy(yn, Tab::B[0], z);
+      Trk<RPL> u6;
+      static_for<Tab::NS - 1>([&](auto kc) {
+        constexpr int kk = 1 + decltype(kc)::value;
+        z = solve(z);
+        trk_axpy(yn, Tab::B[kk], z);
+        if constexpr (kk == 1) u6 = trk_scale(Tab::E[1], z); else trk_axpy(u6, Tab::E[kk], z);
+      });
+
+      double err;
+      if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
+      // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
+      // a rejection too (acc = false), so the state is settled before the non-finite exit below looks at it
+      const bool acc = (err <= 1.0);
+      if constexpr (PARK) {
+        // accepting lanes record the candidate's site rows in their slots (LDS writes under the lane mask instead of a select per dword
+        // of the state); y.s is the candidate from here to the end of the iteration -- only a landing, which is an accept, reads it
+        if (acc) {
+          static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(yn.s[j]); });
+          // the time moves under the same mask: one add where tc = acc ? tc + hs : tc was an add and two selects
+          if constexpr (!CFG::LITERAL) tc += hs;
+        }
 #pragma unroll
-      for (int j = 0; j < RPL; ++j) loc += y.s[j];
-      y.sg = gsum<G>(loc, lane);
-      emit(k, y, std::false_type{});
-      ++k;
+        for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
+        y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; y.sg = acc ? yn.sg : y.sg;
+      } else {
+        if (acc) {
+          y = yn;
+          if constexpr (!CFG::LITERAL) tc += hs;
+        }
+      }
+      if constexpr (CFG::LITERAL) {
+        if (err != err || err > 1e300) {
+          ++nsec; after_reject = true; h = 0.1 * hs;
+          const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
+          if (bad != 0.0 || (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC)) || (nonfinite(Dsum)) || (nonfinite(Scw))) {
+            status |= PK_ST_NONFINITE; break;
+          }
+          continue;
+        }
+      } else {
+        ++nsec;
+        if (__builtin_expect(err != err || err > 1e300, 0)) { after_reject = true; h = 0.1 * hs; nonfin = true; break; }
+      }
+      double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
+      fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+      double hnew = hs * fast_rcp(fac);
+      const bool land = acc && last;
+      if constexpr (CFG::LITERAL) { nacc += acc ? 1 : 0; nsec += acc ? 0 : 1; }
+      else nacc += (int)acc;                            // the predicate itself: 0 or 1
+      if (acc && after_reject) hnew = fmin(hnew, hs);
+      after_reject = !acc;
+      if constexpr (CFG::LITERAL) tc = land ? te : (acc ? tc + hs : tc);
+      h = (land && hs < h) ? fmax(hnew, h) : hnew;
+      if (land) {
+        // a landing sets the time to the output time itself (tc + hs is te only up to rounding); the accept above has already moved
+        // tc, which nothing reads in between
+        if constexpr (!CFG::LITERAL) tc = te;
+        te = tnx;
+        asm volatile("" : "+v"(te));                      // pins this copy ahead of the row's stores: its wait then covers the load of tnx alone
+        // re-sum the sites at every landing so the tracked sum cannot drift
+        double loc = 0.0;
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) loc += y.s[j];
+        y.sg = gsum<G>(loc, lane);
+        emit(k, y, std::false_type{});
+        ++k;
+      }
+      if (k >= T) break;
     }
-    if (k >= T) break;
+    if (CFG::LITERAL || !nonfin) break;
+    // cold: decides exactly as the run-time kernel does in its loop.  y is the accepted state (a NaN or inf error is a rejection), the
+    // coefficients never change, and Scw is the one the rejected step's factor() computed -- nothing ran since
+    const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
+    if (bad != 0.0 || (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC)) || (nonfinite(Dsum)) || (nonfinite(Scw))) {
+      status |= PK_ST_NONFINITE; break;
+    }
   }
+  const int nrej = CFG::LITERAL ? nsec : nsec - nacc;
   if (status != PK_ST_OK)                               // a failed replica: NaN rows from the landing it failed at
     for (; k < T; ++k) emit(k, y, std::true_type{});
   finish(status, nacc, nrej);
