@@ -9,8 +9,9 @@
 //     (site i = lane + G * j), so S = 32 runs EIGHT replicas per wavefront instead of two;
 //   * the two coupling rows (mRNA R and unphosphorylated protein P) are "shadowed": every lane of the group carries
 //     them as wave-uniform-per-group scalars and updates them redundantly, so no broadcast is ever needed;
-//   * the site sum that closes row P is tracked through the stage recurrences (it is linear in the stage vectors), so a
-//     stage costs exactly ONE group reduction (inside the arrow solve), done with DPP moves only;
+//   * the site sum that closes row P is needed once per step (by the right-hand side of the accepted state), so it is formed once per
+//     step: a tree over the candidate's site rows in the lane, then one group reduction, taken over under the accept predicate.  A
+//     stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
 //   * no LDS-pipe instruction in the solve chain; LDS only as thread-private parking space in the PARK layouts (below).
 //
 // dR/dt = A - B R ; dP/dt = C R - (D + sum S_i) P + sum X_i ; dX_i/dt = S_i P - (1 + D_i) X_i
@@ -20,28 +21,34 @@
 namespace pk {
 
 template <int RPL>
-struct Trk {               // one vector of the system as seen by a lane
+struct Stg {               // one vector of the system as seen by a lane: a stage, a candidate, an error estimate
   double s[RPL];           // this lane's site rows
   double R, P;             // shadow rows (identical in every lane of the group)
-  double sg;               // sum over ALL sites of the group (identical in every lane)
+};
+template <int RPL>
+struct Trk : Stg<RPL> {    // the accepted state: the only vector whose site sum is read (by the right-hand side, once per step)
+  double sg;               // sum over ALL sites of the group (identical in every lane): site_sum of the rows above, nothing else
 };
 
 template <int RPL>
-__device__ __forceinline__ void trk_axpy(Trk<RPL>& acc, const double a, const Trk<RPL>& u) {
+__device__ __forceinline__ void trk_axpy(Stg<RPL>& acc, const double a, const Stg<RPL>& u) {
 #pragma unroll
   for (int j = 0; j < RPL; ++j) acc.s[j] = __builtin_fma(a, u.s[j], acc.s[j]);
   acc.R = __builtin_fma(a, u.R, acc.R);
   acc.P = __builtin_fma(a, u.P, acc.P);
-  acc.sg = __builtin_fma(a, u.sg, acc.sg);
 }
 template <int RPL>
-__device__ __forceinline__ Trk<RPL> trk_scale(const double a, const Trk<RPL>& u) {
-  Trk<RPL> r;
+__device__ __forceinline__ Stg<RPL> trk_scale(const double a, const Stg<RPL>& u) {
+  Stg<RPL> r;
 #pragma unroll
   for (int j = 0; j < RPL; ++j) r.s[j] = a * u.s[j];
-  r.R = a * u.R; r.P = a * u.P; r.sg = a * u.sg;
+  r.R = a * u.R; r.P = a * u.P;
   return r;
 }
+// the sum over all sites of a replica: a tree over the lane's rows, then the group reduction (every y.sg of the kernel is this function
+// of the accepted site rows)
+template <int G, int RPL>
+__device__ __forceinline__ double site_sum(const double (&s)[RPL], int lane) { return gsum<G>(tree_sum(s), lane); }
 
 // What is uniform over a launch and chosen by run-time fields of SolveArgs, as a compile-time configuration.  DistFixed names one
 // combination (the launchers pick it when SolveArgs matches); DistAny reads every choice from SolveArgs at run time and serves the rest.
@@ -152,14 +159,12 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   const double* y0p = A.y0 + (A.y0_batched ? rep * S : 0);
   Trk<RPL> y;
   y.R = y0p[0]; y.P = y0p[1];
-  lsum = 0.0;
 #pragma unroll
   for (int j = 0; j < RPL; ++j) {
     const int i = l + G * j;
     y.s[j] = (i < n) ? y0p[2 + i] : 0.0;
-    lsum += y.s[j];
   }
-  y.sg = gsum<G>(lsum, lane);
+  y.sg = site_sum<G>(y.s, lane);
   if constexpr (PARK) static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(y.s[j]); });
 
   // ---- output / fused Morris metric (same semantics as Emitter in pk_solve_kernel.hpp)
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // this lane's first site in the trajectory row of the next output time; advanced by one row per landing
   double* srow = CFG::sol(A) ? A.sol + rep * T * S + 2 + l : nullptr;
   // one output row: nf = std::true_type writes the NaN rows of a failed replica (cold), std::false_type the values of v
-  auto emit = [&](const int k, const Trk<RPL>& v, auto nf) {
+  auto emit = [&](const int k, const Stg<RPL>& v, auto nf) {
     constexpr bool nan_fill = decltype(nf)::value;
     double* fl = CFG::flat(A) ? A.flat + rep * A.F : nullptr;
     // The clip `x < 0 ? 0 : x` (a compare and two selects per double) changes a value only where its sign bit is set: x < 0 is false for
@@ -189,7 +194,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       if (CFG::normalize(A)) r *= 1.0 / y0p[state];
       return r;
     };
-    Trk<RPL> c = v;                                     // the clipped state
+    Stg<RPL> c = v;                                     // the clipped state
     if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
       asm volatile("" : "+v"(c.R));                     // keeps this a branch: without it the compiler folds the test into each select
       c.R = (c.R < 0.0) ? 0.0 : c.R; c.P = (c.P < 0.0) ? 0.0 : c.P;
@@ -281,7 +286,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   const double rtol = A.rtol, atol = A.atol;
   // max-norm helpers over the whole system (sites of this lane + shadows, then across the group)
   auto q = [&](double e, double ya, double yb) { return fabs(e) * approx_rcp(__builtin_fma(rtol, fmax(fabs(ya), fabs(yb)), atol)); };
-  auto group_max = [&](const Trk<RPL>& num, const Trk<RPL>& a, const Trk<RPL>& b) {   // NaN-propagating: the initial step estimate; DistAny
+  auto group_max = [&](const Stg<RPL>& num, const Stg<RPL>& a, const Stg<RPL>& b) {   // NaN-propagating: the initial step estimate; DistAny
     auto mx = [](double p, double r) { return (p > r || p != p) ? p : r; };
     double m = mx(q(num.R, a.R, b.R), q(num.P, a.P, b.P));
 #pragma unroll
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // scale, inf * 0, 0 * inf) is found by unordered compares on pairs of ratios and turned into +inf, which v_max_f64 carries through the
   // group; an inf ratio is the maximum anyway.  The loop treats +inf and NaN alike (reject, then the PK_ST_NONFINITE test), and for finite
   // ratios the maximum has the bits group_max returns.
-  auto err_norm = [&](const Trk<RPL>& e, const Trk<RPL>& y, const Trk<RPL>& yn) {
+  auto err_norm = [&](const Stg<RPL>& e, const Stg<RPL>& y, const Stg<RPL>& yn) {
     double r[RPL + 2];
     r[0] = q(e.R, y.R, yn.R); r[1] = q(e.P, y.P, yn.P);
     static_for<RPL>([&](auto jc) {
@@ -304,15 +309,14 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     if (any_nan(r)) m = __builtin_inf();
     return gmax_num<G>(m, lane);
   };
-  auto rhs_of = [&](const Trk<RPL>& Y) {            // f(Y); .sg unused
-    Trk<RPL> f;
+  auto rhs_of = [&](const Trk<RPL>& Y) {            // f(Y): the one reader of Y.sg
+    Stg<RPL> f;
     f.R = __builtin_fma(-cB, Y.R, cA);
     f.P = __builtin_fma(cC, Y.R, __builtin_fma(-Dsum, Y.P, Y.sg));
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
       f.s[j] = __builtin_fma(pk.template get<K_SR + j>(), Y.P, -pk.template get<K_DG + j>() * Y.s[j]);
     });
-    f.sg = 0.0;
     return f;
   };
 
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   double te = A.t[1];
   double h;
   {
-    const Trk<RPL> f0 = rhs_of(y);
+    const Stg<RPL> f0 = rhs_of(y);
     const double d0 = group_max(y, y, y), d1 = group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
@@ -342,9 +346,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     Scw = gsum<G>(tree_sum(cw), lane);
     sinv = fast_rcp(__builtin_fma(q, Dsum - Scw, 1.0));
   };
-  // u = M^{-1} r   (r.sg ignored; u.sg = sum over sites of u): ONE group reduction
-  auto solve = [&](const Trk<RPL>& r) {
-    Trk<RPL> u;
+  // u = M^{-1} r: ONE group reduction
+  auto solve = [&](const Stg<RPL>& r) {
+    Stg<RPL> u;
     const double xR = r.R * winvR;
     double t[RPL];
 #pragma unroll
@@ -353,7 +357,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), r.P) * sinv;
 #pragma unroll
     for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
-    u.R = xR; u.P = xP; u.sg = __builtin_fma(xP, Scw, St);
+    u.R = xR; u.P = xP;
     return u;
   };
 
@@ -387,9 +391,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       }
       factor(Tab::GAM * hs);
 
-      Trk<RPL> z = solve(trk_scale(hs, rhs_of(y)));
-      Trk<RPL> yn = y; trk_axpy(yn, Tab::B[0], z);
-      Trk<RPL> u6;
+      Stg<RPL> z = solve(trk_scale(hs, rhs_of(y)));
+      Stg<RPL> yn = y; trk_axpy(yn, Tab::B[0], z);
+      Stg<RPL> u6;
       static_for<Tab::NS - 1>([&](auto kc) {
         constexpr int kk = 1 + decltype(kc)::value;
         z = solve(z);
@@ -397,6 +401,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         if constexpr (kk == 1) u6 = trk_scale(Tab::E[1], z); else trk_axpy(u6, Tab::E[kk], z);
       });
 
+      // the candidate's site sum, formed directly (as the C restatement's right-hand side does) and independent of the error norm; an
+      // accepting lane takes it over with R and P, a rejecting lane keeps the sum of the state it keeps
+      const double sg_new = site_sum<G>(yn.s, lane);
       double err;
       if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
       // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
@@ -412,10 +419,10 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         }
 #pragma unroll
         for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
-        y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; y.sg = acc ? yn.sg : y.sg;
+        y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; y.sg = acc ? sg_new : y.sg;
       } else {
         if (acc) {
-          y = yn;
+          static_cast<Stg<RPL>&>(y) = yn; y.sg = sg_new;
           if constexpr (!CFG::LITERAL) tc += hs;
         }
       }
@@ -448,11 +455,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         if constexpr (!CFG::LITERAL) tc = te;
         te = tnx;
         asm volatile("" : "+v"(te));                      // pins this copy ahead of the row's stores: its wait then covers the load of tnx alone
-        // re-sum the sites at every landing so the tracked sum cannot drift
-        double loc = 0.0;
-#pragma unroll
-        for (int j = 0; j < RPL; ++j) loc += y.s[j];
-        y.sg = gsum<G>(loc, lane);
+        // y.sg already is the direct sum of the rows emitted here
         emit(k, y, std::false_type{});
         ++k;
       }
