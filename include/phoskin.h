@@ -335,6 +335,27 @@ int pk_loss_fn_batch_host(pk_ctx*, int combinatorial, int loss_mode, int64_t B, 
  * lists of a pk_loss (protein | rna | phospho, obs / w ignored), floor eps (the reference uses 1e-12 there): pred [B, n_prot+n_rna+n_pho]. */
 int pk_network_observables_batch(pk_ctx*, pk_net*, pk_loss*, int64_t B, const double* Y, int T, double eps, double* pred);
 
+/* simulate + fold-change observables + scalar Morris metric in ONE launch (SURVEY fused op (iii) on the network path: the body of the
+ * reference's sensitivity worker, sensitivity.py:143-168 = simulate_and_measure -> _compute_scalar_metric): the order-3 integrator forms the
+ * fold changes of `lists` (a pk_loss; its obs / w arrays are ignored) at its output times exactly as pk_network_observables_batch forms them
+ * from a stored trajectory (floor eps), and reduces them per candidate to metric [B]:
+ *   PK_NET_METRIC_TOTAL_SIGNAL sum p, _MEAN sum p / n, _VARIANCE the population variance (Welford partials merged pairwise in a fixed order,
+ *   never E[p^2] - E[p]^2), _L2_NORM sqrt(sum p^2); all four are 0.0 for empty lists.  A candidate's value does not depend on B.
+ * pred [B, n_prot + n_rna + n_pho] (optional) receives the fold changes in the order of the lists as they were given to
+ * pk_network_loss_create; Y [B,T,S] (optional) the trajectory; at least one of metric, pred, Y must be non-NULL.  status, n_steps and Y equal
+ * pk_network_simulate_batch's for the same opts bit for bit.  A flagged candidate (status != 0) gets metric = NaN and an all-NaN pred row.
+ * Runs wherever the plan for opts (pk_network_resolve_method) is PK_METHOD_ROS34PW2 on the general LDS kernel or on the workspace kernel --
+ * by default on networks beyond one workgroup -- and moves from the LDS kernel to the workspace kernel where the LDS request (N doubles
+ * more than a plain launch: the rna baseline) passes 160 KiB.  PK_ERR_UNSUPPORTED, with the remedy in pk_last_error: a plan on the
+ * register-resident kernels (ask for the LDS kernel: opts->linsolve = PK_LINSOLVE_STRUCTURED), on PK_METHOD_ARK436 or PK_METHOD_DP5 (ask for
+ * PK_METHOD_ROS34PW2), lists whose protein / phospho baseline is not time index 0 or that hold an rna observation before the rna baseline
+ * (call pk_network_simulate_batch + pk_network_observables_batch).  PK_ERR_ARG: metric_id outside 0..3; metric, pred and Y all NULL.
+ * x, y0, Y, pred, metric, status, n_steps: DEVICE pointers; t: HOST. */
+enum { PK_NET_METRIC_TOTAL_SIGNAL = 0, PK_NET_METRIC_MEAN = 1, PK_NET_METRIC_VARIANCE = 2, PK_NET_METRIC_L2_NORM = 3 };
+int pk_network_simulate_measure_batch(pk_ctx*, pk_net*, pk_loss* lists, int64_t B, const double* x, int x_is_raw, const double* y0,
+                                      int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, double eps, int metric_id,
+                                      double* Y, double* pred, double* metric, int32_t* status, int32_t* n_steps);
+
 /* Timing hook for bench.py: runs `iters` back-to-back launches of pk_solve_protein_batch on the context's
  * stream between two hipEvents and returns the mean kernel time per launch in milliseconds (< 0 on error). */
 double pk_time_solve_protein_batch(pk_ctx*, int iters, int model, int n_sites, int64_t B,

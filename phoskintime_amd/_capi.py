@@ -68,12 +68,15 @@ SYMBOLS = (
     "pk_time_solve_protein_batch", "pk_measure_hbm_gbs", "pk_measure_hbm_stream_gbs", "pk_measure_fp64_fma_tflops",
     "pk_network_create", "pk_network_destroy", "pk_network_n_states", "pk_network_n_var",
     "pk_network_rhs_batch", "pk_network_jacobian_batch", "pk_network_unpack_batch", "pk_network_simulate_batch",
-    "pk_network_loss_create", "pk_network_loss_destroy", "pk_network_objective_batch", "pk_network_simulate_objective_batch", "pk_network_observables_batch", "pk_frechet_batch", "pk_loss_fn_batch_host", "pk_network_resolve_method",
+    "pk_network_loss_create", "pk_network_loss_destroy", "pk_network_objective_batch", "pk_network_simulate_objective_batch", "pk_network_observables_batch", "pk_network_simulate_measure_batch", "pk_frechet_batch", "pk_loss_fn_batch_host", "pk_network_resolve_method",
     "pk_network_workspace_bytes",
     "pk_comm_unique_id", "pk_comm_init", "pk_comm_rank", "pk_comm_world", "pk_allgather_f64", "pk_comm_destroy",
 )
 
 PK_OK, PK_ERR_ARG, PK_ERR_UNSUPPORTED, PK_ERR_HIP, PK_ERR_NOMEM = 0, -1, -2, -3, -4      # include/phoskin.h
+# PK_NET_METRIC_*: the scalar metrics of pk_network_simulate_measure_batch, by the names of sensitivity._compute_scalar_metric
+NET_METRIC_TOTAL_SIGNAL, NET_METRIC_MEAN, NET_METRIC_VARIANCE, NET_METRIC_L2_NORM = 0, 1, 2, 3
+NET_METRICS = {"total_signal": NET_METRIC_TOTAL_SIGNAL, "mean": NET_METRIC_MEAN, "variance": NET_METRIC_VARIANCE, "l2_norm": NET_METRIC_L2_NORM}
 
 _lib = None
 
@@ -140,6 +143,8 @@ def load():
     lib.pk_network_simulate_objective_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, optp, i32, vp, vp, dbl, vp, vp, vp, vp, vp]
     lib.pk_network_observables_batch.restype = i32
     lib.pk_network_observables_batch.argtypes = [vp, vp, vp, i64, vp, i32, dbl, vp]
+    lib.pk_network_simulate_measure_batch.restype = i32
+    lib.pk_network_simulate_measure_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, optp, dbl, i32, vp, vp, vp, vp, vp]
     lib.pk_network_resolve_method.restype = i32; lib.pk_network_resolve_method.argtypes = [vp, optp]
     lib.pk_network_workspace_bytes.restype = i64; lib.pk_network_workspace_bytes.argtypes = [vp, vp, i64]
     lib.pk_loss_fn_batch_host.restype = i32

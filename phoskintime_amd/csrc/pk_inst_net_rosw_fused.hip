@@ -1,5 +1,5 @@
 // Instantiations + launchers of the order-3 network integrator that scores the three-objective loss as it integrates
-// (net_rosw_solve<MODEL, FUSED = true>, pk_network_solve.hpp): the LDS kernel and the workspace kernel, topologies 0 / 1 / 2 / 4.
+// (net_rosw_solve<MODEL, SCORE_LOSS>, pk_network_solve.hpp): the LDS kernel and the workspace kernel, topologies 0 / 1 / 2 / 4.
 #include "pk_network_solve.hpp"
 
 namespace pk {
@@ -37,8 +37,8 @@ hipError_t launch_net_ws_fused(const NetDev& n, const NetSolveArgs& a, long long
 hipError_t launch_net_lds_fused(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st) {
 #define PK_FUSED_LAUNCH(M)                                                                                                            \
   do {                                                                                                                                \
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)net_solve_kernel<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((net_solve_kernel<M, true>), dim3((unsigned)B), dim3(threads), lds, st, n, a);                                  \
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)net_solve_kernel<M, SCORE_LOSS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    hipLaunchKernelGGL((net_solve_kernel<M, SCORE_LOSS>), dim3((unsigned)B), dim3(threads), lds, st, n, a);                                  \
   } while (0)
   switch (n.model) {
     case 0: PK_FUSED_LAUNCH(0); break;

@@ -20,6 +20,10 @@ hipError_t launch_net_ws(const NetDev& n, const NetSolveArgs& a, long long B, in
 hipError_t net_ws_fused_grid(const NetDev& n, long long B, int* grid);
 hipError_t launch_net_ws_fused(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
 hipError_t launch_net_lds_fused(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st);
+// ... and measuring the fold-change observables and their scalar Morris metric (pk_inst_net_rosw_measure.hip)
+hipError_t net_ws_measure_grid(const NetDev& n, long long B, int* grid);
+hipError_t launch_net_ws_measure(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
+hipError_t launch_net_lds_measure(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
@@ -357,7 +361,8 @@ int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { ret
 
 // `fused`: null, or the loss fields of NetSolveArgs filled in (pk_network_simulate_objective_batch); Y may then be null.  With
 // fused->loss_ptr set (the time-bucketed lists: the caller asked for the order-3 method or the workspace kernel) the launch runs where the
-// plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel
+// plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel.  fused->meas: the same lists measured
+// instead of scored (pk_network_simulate_measure_batch), on the same two kernels
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                              const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps,
                              const pk::NetSolveArgs* fused) {
@@ -371,6 +376,16 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   NetPlan plan = net_plan(n, opts_in);
   if (plan.code != PK_OK) return pk_ctx_fail(c, plan.code, plan.refusal);
   const bool rosw_fused = fused && fused->loss_ptr;
+  const bool measure = rosw_fused && fused->meas;
+  if (measure) {
+    if (plan.kernel == NetKernel::Reg || plan.kernel == NetKernel::CombReg)
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused measurement: not on the register-resident kernels; ask for the general LDS kernel "
+                                                "(opts->linsolve = PK_LINSOLVE_STRUCTURED, kernel = \"lds\" in Python) or PK_KERNEL_WORKSPACE");
+    if (plan.kernel != NetKernel::Lds && plan.kernel != NetKernel::Workspace)
+      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused measurement: the order-3 integrator only; ask for opts->method = PK_METHOD_ROS34PW2 (method = \"rosw\" in "
+                                                "Python) on the general LDS kernel or the workspace kernel, or call pk_network_simulate_batch + "
+                                                "pk_network_observables_batch");
+  }
   if (rosw_fused) {
     if (plan.kernel == NetKernel::Reg || plan.kernel == NetKernel::CombReg)
       return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective with PK_METHOD_ROS34PW2: not on the register-resident kernels; ask for the general LDS "
@@ -414,6 +429,8 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
     for (int k = 0; k < 4; ++k) a.loss_lam[k] = fused->loss_lam[k];
     for (int k = 0; k < 3; ++k) a.loss_norm[k] = fused->loss_norm[k];
     a.loss_ptr = fused->loss_ptr; a.loss_prot = fused->loss_prot; a.loss_site = fused->loss_site; a.loss_lobs = fused->loss_lobs; a.loss_lw = fused->loss_lw;
+    a.meas = fused->meas; a.meas_id = fused->meas_id; a.meas_n = fused->meas_n; a.meas_eps = fused->meas_eps;
+    a.meas_perm = fused->meas_perm; a.meas_pred = fused->meas_pred; a.meas_metric = fused->meas_metric;
     if (!rosw_fused && !(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
       return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: topologies 0 / 1 / 4 on the default additive integrator only; "
                                                 "use pk_network_simulate_batch + pk_network_objective_batch");
@@ -445,15 +462,17 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   switch (plan.kernel) {
     case NetKernel::Workspace: {
       // ROS34PW2 on workspace slabs (net_solve_ws_kernel): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
-      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; bool fused; } q{&n->d, &a, (long long)B, 0, rosw_fused};
-      if ((rosw_fused ? pk::net_ws_fused_grid(n->d, (long long)B, &q.grid) : pk::net_ws_grid(n->d, (long long)B, &q.grid)) != hipSuccess)
+      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; bool fused, measure; } q{&n->d, &a, (long long)B, 0, rosw_fused, measure};
+      if ((measure ? pk::net_ws_measure_grid(n->d, (long long)B, &q.grid) : rosw_fused ? pk::net_ws_fused_grid(n->d, (long long)B, &q.grid)
+                                                                                      : pk::net_ws_grid(n->d, (long long)B, &q.grid)) != hipSuccess)
         return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
       auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
         const Q& r = *(const Q*)user;
-        return r.fused ? pk::launch_net_ws_fused(*r.d, *r.a, r.B, r.grid, (double*)scratch, s)
-                       : pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
+        return r.measure ? pk::launch_net_ws_measure(*r.d, *r.a, r.B, r.grid, (double*)scratch, s)
+               : r.fused ? pk::launch_net_ws_fused(*r.d, *r.a, r.B, r.grid, (double*)scratch, s)
+                         : pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
       };
-      // a fused launch's slab is N doubles longer (the rna baseline)
+      // a fused launch's slab is N doubles longer (the rna baseline), a measuring launch's too
       const size_t slab = rosw_fused ? pk::net_ws_fused_slab_doubles(n->d) : pk::net_ws_slab_doubles(n->d);
       return pk_ctx_scratch_launch(c, (size_t)q.grid * slab * sizeof(double), launch, &q);
     }
@@ -514,7 +533,9 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       int threads = (n->d.S <= 128 && n->d.N <= 64) ? 64 : 256;        // measured at S = 500: 256 threads beat 128 by 1.33x
       if (const char* e = getenv("PK_NET_THREADS")) { const int v = atoi(e); if ((v == 64 || v == 128 || v == 256) && n->d.S <= 4 * v && n->d.N <= 2 * v) threads = v; }
       if (rosw_fused) {
-        const hipError_t ef = pk::launch_net_lds_fused(n->d, a, (long long)B, threads, pk::net_solve_fused_lds_bytes(n->d, n->nnzT), stream);
+        const size_t lb = pk::net_solve_fused_lds_bytes(n->d, n->nnzT);
+        const hipError_t ef = measure ? pk::launch_net_lds_measure(n->d, a, (long long)B, threads, lb, stream)
+                                      : pk::launch_net_lds_fused(n->d, a, (long long)B, threads, lb, stream);
         if (ef != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(ef));
         break;
       }
@@ -575,6 +596,30 @@ int pk_network_simulate_objective_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_
   f.loss_defaults = defaults; f.loss_mode = loss_mode; f.loss_fail = fail_value; f.loss_sums = loss_sums; f.loss_F = F;
   f.loss_lam[0] = lambdas ? lambdas[0] : 1.0; f.loss_lam[1] = lambdas ? lambdas[1] : 1.0; f.loss_lam[2] = lambdas ? lambdas[2] : 1.0;
   f.loss_lam[3] = lambdas ? lambdas[3] : 0.0;
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps, &f);
+}
+
+// simulate + fold-change observables + scalar Morris metric in ONE launch (SURVEY fused op (iii) on the network path; the reference's
+// sensitivity worker, sensitivity.py:143-168): the order-3 LDS / workspace kernels measure the handle's time-bucketed index lists at their
+// output rows and reduce them per candidate.  Same status / n_steps / Y as pk_network_simulate_batch for the same opts; pred equals
+// pk_network_observables_batch on that trajectory (same operands, same order).
+int pk_loss_measure_lists(const pk_loss* l, const int32_t** ptr, const int32_t** prot, const int32_t** site, const int32_t** perm, int* n_obs,
+                          int* T, int* rna_base);
+int pk_network_simulate_measure_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_t B, const double* x, int x_is_raw, const double* y0,
+                                      int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, double eps, int metric_id,
+                                      double* Y, double* pred, double* metric, int32_t* status, int32_t* n_steps) {
+  if (!c || !n || !l) return PK_ERR_ARG;
+  if (metric_id < PK_NET_METRIC_TOTAL_SIGNAL || metric_id > PK_NET_METRIC_L2_NORM) return pk_ctx_fail(c, PK_ERR_ARG, "metric_id must be PK_NET_METRIC_* (0..3)");
+  if (B == 0) return PK_OK;
+  if (!metric && !pred && !Y) return pk_ctx_fail(c, PK_ERR_ARG, "metric, pred and Y are all NULL: nothing to compute");
+  pk::NetSolveArgs f;
+  std::memset(&f, 0, sizeof(f));
+  int Tl = 0;
+  if (!pk_loss_measure_lists(l, &f.loss_ptr, &f.loss_prot, &f.loss_site, &f.meas_perm, &f.meas_n, &Tl, &f.loss_rna_base))
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused measurement: protein / phospho baselines must be time index 0 and rna observations not earlier than "
+                                              "the rna baseline; call pk_network_simulate_batch + pk_network_observables_batch");
+  if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the index lists were created for");
+  f.meas = 1; f.meas_id = metric_id; f.meas_eps = eps; f.meas_pred = pred; f.meas_metric = metric;
   return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps, &f);
 }
 

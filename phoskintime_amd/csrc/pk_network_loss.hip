@@ -194,6 +194,8 @@ struct pk_loss {
   // each output row.  Any topology, and a (state, time) may be observed twice; null under the two baseline conditions above
   const int32_t* lc_ptr = nullptr; const int32_t* lc_prot = nullptr; const int32_t* lc_site = nullptr;
   const double* lc_obs = nullptr; const double* lc_w = nullptr;
+  // bucketed entry -> its position in the caller's (protein | rna | phospho) lists: where the fused measurement stores its fold change
+  const int32_t* lc_perm = nullptr;
 };
 
 namespace {
@@ -265,7 +267,7 @@ pk_loss* pk_network_loss_create(pk_ctx* c, pk_net* net, const pk_loss_data* d, i
   if (ok && d->prot_base_idx == 0 && d->pho_base_idx == 0 && rna_after_base) {
     // stable counting sort of each modality by time index into one set of arrays (protein | rna | phospho)
     const size_t tot = (size_t)d->n_prot + d->n_rna + d->n_pho, T1 = (size_t)T + 1;
-    std::vector<int32_t> ptr(3 * T1, 0), pr(tot, 0), si(tot, 0);
+    std::vector<int32_t> ptr(3 * T1, 0), pr(tot, 0), si(tot, 0), perm(tot, 0);
     std::vector<double> ob(tot, 0.0), wt(tot, 0.0);
     const int cnt[3] = {d->n_prot, d->n_rna, d->n_pho};
     const int32_t* tt[3] = {d->t_prot, d->t_rna, d->t_pho};
@@ -281,12 +283,12 @@ pk_loss* pk_network_loss_create(pk_ctx* c, pk_net* net, const pk_loss_data* d, i
       std::vector<int32_t> fill(pm, pm + T);
       for (int k = 0; k < cnt[m]; ++k) {
         const int at = fill[tt[m][k]]++;
-        pr[at] = pp[m][k]; si[at] = (m == 2) ? d->s_pho[k] : 0; ob[at] = oo[m][k]; wt[at] = ww[m][k];
+        pr[at] = pp[m][k]; si[at] = (m == 2) ? d->s_pho[k] : 0; ob[at] = oo[m][k]; wt[at] = ww[m][k]; perm[at] = (int32_t)first + k;
       }
       first += (size_t)cnt[m];
     }
     l->lc_ptr = up(l, ptr.data(), ptr.size(), ok); l->lc_prot = up(l, pr.data(), tot, ok); l->lc_site = up(l, si.data(), tot, ok);
-    l->lc_obs = up(l, ob.data(), tot, ok); l->lc_w = up(l, wt.data(), tot, ok);
+    l->lc_obs = up(l, ob.data(), tot, ok); l->lc_w = up(l, wt.data(), tot, ok); l->lc_perm = up(l, perm.data(), tot, ok);
   }
   if (!ok) { pk_ctx_fail(c, PK_ERR_NOMEM, "hipMalloc / hipMemcpy failed"); pk_network_loss_destroy(l); return nullptr; }
   return l;
@@ -299,6 +301,16 @@ int pk_loss_fused_lists(const pk_loss* l, const int32_t** ptr, const int32_t** p
   if (!l || !l->lc_ptr) return 0;
   *ptr = l->lc_ptr; *prot = l->lc_prot; *site = l->lc_site; *obs = l->lc_obs; *w = l->lc_w;
   norms[0] = l->d.norm_p; norms[1] = l->d.norm_r; norms[2] = l->d.norm_ph; *T = l->T; *rna_base = l->d.base_rna;
+  return 1;
+}
+
+// for the fused measurement of the order-3 kernels (pk_network.hip): the bucketed index lists, their permutation back to the caller's order,
+// the number of entries, the grid length and the rna baseline row; 0 under the same two conditions
+int pk_loss_measure_lists(const pk_loss* l, const int32_t** ptr, const int32_t** prot, const int32_t** site, const int32_t** perm, int* n_obs,
+                          int* T, int* rna_base) {
+  if (!l || !l->lc_ptr || !l->lc_perm) return 0;
+  *ptr = l->lc_ptr; *prot = l->lc_prot; *site = l->lc_site; *perm = l->lc_perm;
+  *n_obs = l->d.n_prot + l->d.n_rna + l->d.n_pho; *T = l->T; *rna_base = l->d.base_rna;
   return 1;
 }
 

@@ -51,11 +51,19 @@ struct NetSolveArgs {
   const double* loss_obs; const double* loss_w; const double* loss_defaults;
   double loss_lam[4], loss_norm[3], loss_fail; int loss_mode, loss_rna_base;
   double* loss_sums; double* loss_F;
-  // fused objective of the order-3 kernels (net_rosw_solve<.., FUSED = true>): the loss handle's observation lists bucketed by time index
+  // fused objective of the order-3 kernels (net_rosw_solve<.., SCORE_LOSS>): the loss handle's observation lists bucketed by time index
   // instead of the dense tables.  One set of arrays (protein | rna | phospho, each sorted by time index); modality m's observations of
   // output row t are entries loss_ptr[m (T + 1) + t] .. loss_ptr[m (T + 1) + t + 1].  loss_site: phospho entries only
   const int32_t* loss_ptr; const int32_t* loss_prot; const int32_t* loss_site; const double* loss_lobs; const double* loss_lw;
+  // fused measurement of the order-3 kernels (net_rosw_solve<.., SCORE_MEASURE>, pk_network_simulate_measure_batch): the same bucketed lists
+  // (loss_ptr / loss_prot / loss_site; loss_rna_base), observations and weights unused.  meas_perm: bucketed entry -> its position in the
+  // caller's (protein | rna | phospho) lists; meas_pred [B, meas_n] and meas_metric [B] are optional; meas_id: PK_NET_METRIC_*
+  int meas; int meas_id; int meas_n; double meas_eps;
+  const int32_t* meas_perm; double* meas_pred; double* meas_metric;
 };
+
+// What the order-3 body does with an output row besides storing it: nothing, the three-objective loss, or the scalar Morris metric
+enum NetScore : int { SCORE_NONE = 0, SCORE_LOSS = 1, SCORE_MEASURE = 2 };
 
 // block-wide NaN-propagating max; `red` holds >= 17 doubles of LDS
 __device__ __forceinline__ double block_max(double v, double* red) {
@@ -89,6 +97,29 @@ __device__ __forceinline__ double err_acc(double a, double q, const bool rms) {
   return rms ? __builtin_fma(q, q, a) : ((q > a || q != q) ? q : a);
 }
 
+// Chan's pairwise merge of two Welford triples (count, mean, M2): (n, m, q) <- (n, m, q) + (nb, mb, qb).  Two empty sides stay empty
+__device__ __forceinline__ void welford_merge(double& n, double& m, double& q, const double nb, const double mb, const double qb) {
+  const double nn = n + nb, d = mb - m;
+  const double r = nn > 0.0 ? nb / nn : 0.0;
+  q = q + qb + d * d * n * r;
+  m = m + d * r;
+  n = nn;
+}
+// block-wide merge of per-thread Welford triples in a fixed order: a butterfly within the wave (the lower lane's triple is always the
+// left operand, so every lane of a wave ends with the same bits), then the waves in increasing order through `red` (>= 12 doubles)
+__device__ __forceinline__ void block_welford(double& n, double& m, double& q, double* red) {
+  for (int off = 1; off < 64; off <<= 1) {
+    const double nb = __shfl_xor(n, off), mb = __shfl_xor(m, off), qb = __shfl_xor(q, off);
+    if (threadIdx.x & off) { double n2 = nb, m2 = mb, q2 = qb; welford_merge(n2, m2, q2, n, m, q); n = n2; m = m2; q = q2; }
+    else welford_merge(n, m, q, nb, mb, qb);
+  }
+  const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red[3 * w] = n; red[3 * w + 1] = m; red[3 * w + 2] = q; }
+  __syncthreads();
+  n = red[0]; m = red[1]; q = red[2];
+  for (int i = 1; i < nw; ++i) welford_merge(n, m, q, red[3 * i], red[3 * i + 1], red[3 * i + 2]);
+}
 
 // Per-candidate work area of the integrator: NetLds, then [Ys | U1..U4 | R | winv] (S each) and [sinv | cR | gP] (N each)
 __host__ __device__ inline size_t net_rosw_doubles(const NetDev& n) { return NetLds::doubles(n) + 7 * (size_t)n.S + 3 * (size_t)n.N; }
@@ -160,13 +191,20 @@ struct NetWsLayout {
 // ROS34PW2-W of candidate b, from loading x and y0 to the status / n_steps write.  L: the candidate's NetLds; base: its stage vectors
 // (net_rosw_doubles - NetLds::doubles of them); red: >= 24 doubles of LDS for the reductions.
 //
-// FUSED: the candidate is scored as it integrates (pk_network_simulate_objective_batch on request of the order-3 method): at the initial
+// SCORE_LOSS: the candidate is scored as it integrates (pk_network_simulate_objective_batch on request of the order-3 method): at the initial
 // row and after every landing that fills an output row, the observations of that time index (A.loss_ptr ...) are scored from y -- what
 // net_objective_kernel (pk_network_loss.hip) computes from a stored trajectory, into three per-thread partial sums.  Baselines: y0 for
 // protein / phospho (time index 0); the mRNA values at output row A.loss_rna_base, kept in rbase (N doubles) from the landing that
 // produces them (no rna observation is earlier: the host checks).  The trajectory is written only if A.Y != null.  The plain
 // instantiation has none of this: its A.Y is never null and rbase is unused.
-template <int MODEL, bool FUSED, class Layout>
+//
+// SCORE_MEASURE: the same walk over the same buckets, but each entry's fold change is the measurement itself
+// (pk_network_simulate_measure_batch): formed as net_observables_kernel forms it from a stored trajectory -- same sums in the same order,
+// floor A.meas_eps --, stored at meas_pred[b, meas_perm[k]] when asked for, and folded into the per-thread partial of metric A.meas_id: a
+// sum (total signal, mean), a sum of squares (L2 norm) or a Welford triple (variance; never E[p^2] - E[p]^2: fold changes run from 0.2
+// to several thousand).  The partials are merged in a fixed order (block_sum / block_welford), so a candidate's value does not depend
+// on the batch it shares a launch with.  A flagged candidate gets metric = NaN and an all-NaN pred row.
+template <int MODEL, NetScore SCORE, class Layout>
 __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveArgs& A, const Layout& lay, const long long b, NetLds L,
                                                double* const base, double* const red, double* const rbase = nullptr) {
   using namespace rosw;
@@ -192,18 +230,35 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
   const double* xb = A.x + b * n.n_var;
   for (int k = tid; k < n.n_var; k += nt) L.p[k] = A.x_is_raw ? softplus(xb[k]) : xb[k];
   const double* y0 = A.y0 + (A.y0_batched ? b * S : 0);
-  const bool wY = !FUSED || A.Y != nullptr;
+  constexpr bool FUSED = SCORE == SCORE_LOSS, MEASURE = SCORE == SCORE_MEASURE;
+  const bool wY = SCORE == SCORE_NONE || A.Y != nullptr;
   double* Yout = wY ? A.Y + b * (size_t)A.T * S : nullptr;
   for (int k = tid; k < S; k += nt) { const double v = y0[k]; y[k] = v; if (wY) Yout[k] = v; }
   __syncthreads();
 
-  // ---- fused objective: score output row `row`, which y holds (a barrier lies behind its last write, and none of y changes before the
-  // next one).  Partial sums and the non-finite flag are per thread and per candidate
+  // ---- fused objective / measurement: score output row `row`, which y holds (a barrier lies behind its last write, and none of y changes
+  // before the next one).  Partial sums, the Welford triple and the non-finite flag are per thread and per candidate
   double lacc[3] = {0.0, 0.0, 0.0};
   bool ybad = false;
-  auto score_row = [&](const int row) {
+  double wn = 0.0, wm = 0.0, wq = 0.0;      // MEASURE: (count, mean, M2) of the variance; wm alone is the sum / the sum of squares otherwise
+  double* const predb = (MEASURE && A.meas_pred) ? A.meas_pred + b * (size_t)A.meas_n : nullptr;
+  // entry k of modality m with numerator a and baseline c: one term of the loss, or one measured fold change
+  auto entry = [&](const int m, const int k, const double a, const double c) {
     if constexpr (FUSED) {
-      for (int k = tid; k < S; k += nt) if (nonfinite(y[k])) ybad = true;          // np.all(np.isfinite(Y)) of the reference (optproblem.py:130)
+      const double obs = A.loss_lobs[k], pred = fold_change(a, c);
+      lacc[m] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+    } else if constexpr (MEASURE) {
+      const double eps = A.meas_eps;
+      const double p = (a > eps ? a : eps) / (c > eps ? c : eps);
+      if (predb) predb[A.meas_perm[k]] = p;
+      if (A.meas_id == PK_NET_METRIC_VARIANCE) { wn += 1.0; const double d = p - wm; wm += d / wn; wq += d * (p - wm); }
+      else if (A.meas_id == PK_NET_METRIC_L2_NORM) wm += p * p;
+      else wm += p;
+    }
+  };
+  auto score_row = [&](const int row) {
+    if constexpr (SCORE != SCORE_NONE) {
+      if constexpr (FUSED) for (int k = tid; k < S; k += nt) if (nonfinite(y[k])) ybad = true;   // np.all(np.isfinite(Y)) of the reference (optproblem.py:130)
       if (row == A.loss_rna_base) {
         for (int i = tid; i < N; i += nt) rbase[i] = y[n.offset_y[i]];
         __syncthreads();
@@ -215,13 +270,11 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
         const int cnt = (model == 2) ? (1 << n.n_sites[i]) : 1 + n.n_sites[i];
         double tt = 0.0, tb = 0.0;
         for (int m = 0; m < cnt; ++m) { tt += y[st + 1 + m]; tb += y0[st + 1 + m]; }
-        const double obs = A.loss_lobs[k], pred = fold_change(tt, tb);
-        lacc[0] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+        entry(0, k, tt, tb);
       }
       for (int k = ptr[T1] + tid; k < ptr[T1 + 1]; k += nt) {                      // rna: the mRNA row against the kept baseline
         const int i = A.loss_prot[k];
-        const double obs = A.loss_lobs[k], pred = fold_change(y[n.offset_y[i]], rbase[i]);
-        lacc[1] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+        entry(1, k, y[n.offset_y[i]], rbase[i]);
       }
       for (int k = ptr[2 * T1] + tid; k < ptr[2 * T1 + 1]; k += nt) {              // phospho: site row / all masks with the site's bit
         const int i = A.loss_prot[k], st = n.offset_y[i], j = A.loss_site[k];
@@ -231,8 +284,7 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
           const int cnt = 1 << n.n_sites[i];
           for (int m = 0; m < cnt; ++m) if (m & (1 << j)) { a += y[st + 1 + m]; c += y0[st + 1 + m]; }
         } else { a = y[st + 2 + j]; c = y0[st + 2 + j]; }
-        const double obs = A.loss_lobs[k], pred = fold_change(a, c);
-        lacc[2] += A.loss_lw[k] * point_loss(A.loss_mode, obs - pred, obs, pred);
+        entry(2, k, a, c);
       }
     }
   };
@@ -475,13 +527,28 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
       }
     }
   }
+  if constexpr (MEASURE) {
+    // _compute_scalar_metric of the reference (sensitivity.py:117-140) over the candidate's fold changes; empty lists give 0
+    const double cnt = (double)A.meas_n, qnan = __builtin_nan("");
+    double val;
+    if (A.meas_id == PK_NET_METRIC_VARIANCE) { block_welford(wn, wm, wq, red); val = wn > 0.0 ? wq / wn : 0.0; }
+    else {
+      const double sum = block_sum(wm, red);
+      val = A.meas_id == PK_NET_METRIC_L2_NORM ? sqrt(sum) : (A.meas_id == PK_NET_METRIC_MEAN && A.meas_n > 0) ? sum / cnt : sum;
+    }
+    if (status != PK_ST_OK) {
+      val = qnan;                                        // a barrier of the reduction lies between the entries written above and these
+      if (predb) for (int k = tid; k < A.meas_n; k += nt) predb[k] = qnan;
+    }
+    if (tid == 0 && A.meas_metric) A.meas_metric[b] = val;
+  }
 }
 
 __host__ __device__ inline size_t net_solve_lds_bytes(const NetDev& n, int nnzT);
 
-// One workgroup per candidate, everything in dynamic LDS: the work area, 24 doubles of reductions, then the TF CSR (FUSED: then the
-// rna baseline, N doubles)
-template <int MODEL, bool FUSED = false>
+// One workgroup per candidate, everything in dynamic LDS: the work area, 24 doubles of reductions, then the TF CSR (scoring flavours:
+// then the rna baseline, N doubles)
+template <int MODEL, NetScore SCORE = SCORE_NONE>
 __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const NetSolveArgs A) {
   extern __shared__ __align__(16) double lds[];
   const int N = n.N, nnzT = n.TF_indptr[N];
@@ -495,8 +562,8 @@ __global__ __launch_bounds__(256, 3) void net_solve_kernel(const NetDev n, const
   for (int k = tid; k <= N; k += nt) tf_ptr[k] = n.TF_indptr[k];
   for (int k = tid; k < N; k += nt) tf_deg[k] = n.tf_deg[k];
   const NetRegLayout lay(n, tf_dat, tf_deg, tf_ptr, tf_idx);
-  net_rosw_solve<MODEL, FUSED>(n, A, lay, blockIdx.x, NetLds(lds, n), lds + NetLds::doubles(n), red,
-                               FUSED ? lds + net_solve_lds_bytes(n, nnzT) / 8 : nullptr);
+  net_rosw_solve<MODEL, SCORE>(n, A, lay, blockIdx.x, NetLds(lds, n), lds + NetLds::doubles(n), red,
+                               SCORE != SCORE_NONE ? lds + net_solve_lds_bytes(n, nnzT) / 8 : nullptr);
 }
 
 // Networks of any size: every per-candidate vector in a slab of an HBM workspace instead of LDS, so nothing limits S or N but device
@@ -512,14 +579,14 @@ __global__ __launch_bounds__(256) void net_solve_ws_kernel(const NetDev n, const
   const NetWsLayout lay(n);
   for (long long b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();                                   // the previous candidate of this workgroup is done with the slab
-    net_rosw_solve<MODEL, false>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red);
+    net_rosw_solve<MODEL, SCORE_NONE>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red);
   }
 }
 
-// The same persistent grid scoring the loss (net_rosw_solve<MODEL, true>); the slab is N doubles longer: the rna baseline, behind the work
+// The same persistent grid scoring the loss or the Morris metric (net_rosw_solve<MODEL, SCORE_LOSS / SCORE_MEASURE>); the slab is N doubles longer: the rna baseline, behind the work
 // area.  A kernel of its own so that the plain one keeps its attributes: scoring costs 15 VGPRs (134-136), one workgroup per CU less than
 // the plain kernel's four; held to 128 here (12-20 B of scratch per lane) the resident grid stays 1 024
-template <int MODEL>
+template <int MODEL, NetScore SCORE = SCORE_LOSS>
 __global__ __launch_bounds__(256, 4) void net_solve_ws_fused_kernel(const NetDev n, const NetSolveArgs A, const long long B, double* __restrict__ ws,
                                                                     const size_t slab) {
   __shared__ double red[24];
@@ -527,7 +594,7 @@ __global__ __launch_bounds__(256, 4) void net_solve_ws_fused_kernel(const NetDev
   const NetWsLayout lay(n);
   for (long long b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();                                   // the previous candidate of this workgroup is done with the slab (rna baseline included)
-    net_rosw_solve<MODEL, true>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red, base0 + net_rosw_doubles(n));
+    net_rosw_solve<MODEL, SCORE>(n, A, lay, b, NetLds(base0, n), base0 + NetLds::doubles(n), red, base0 + net_rosw_doubles(n));
   }
 }
 

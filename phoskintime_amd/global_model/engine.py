@@ -39,6 +39,7 @@ class NetworkEngine:
         self._h = self.ctx.lib.pk_network_create(self.ctx.handle, C.byref(d))
         if not self._h:
             raise _capi.PhoskinError("pk_network_create failed: " + (self.ctx.lib.pk_last_error(self.ctx.handle) or b"").decode())
+        self._n_obs = {}                     # index-list handle -> n_prot + n_rna + n_pho (make_loss .. free_loss)
         self.S = self.ctx.lib.pk_network_n_states(self._h)
         self.n_var = self.ctx.lib.pk_network_n_var(self._h)
 
@@ -241,6 +242,68 @@ class NetworkEngine:
         F._keepalive = (xd, yd, dd)  # type: ignore[attr-defined]
         return sums, F, status, nsteps, Y
 
+    def simulate_measure_batch(self, lists, x, t_eval, y0=None, raw: bool = False, rtol: Optional[float] = None, atol: Optional[float] = None,
+                               max_steps: int = 1000000, metric: str = "total_signal", eps: float = 1e-12, want_pred: bool = False,
+                               want_Y: bool = False, method: str = "auto", kernel: str = "auto"):
+        """simulate_odeint -> fold-change observables -> ``_compute_scalar_metric`` (the reference's sensitivity worker, sensitivity.py:143-168)
+        for B candidates in ONE launch: the order-3 integrator measures the index lists ``lists`` (``make_index_lists`` / ``make_loss``;
+        observations and weights ignored) at its output times and reduces them per candidate; neither the trajectory nor the observables
+        reach HBM unless asked for.  Returns (metric [B], pred [B, n_obs] or None, status [B], n_steps [B, 2], Y [B, T, S] or None):
+        ``pred`` (``want_pred``) equals ``observables_batch`` of the trajectory ``simulate_batch`` returns for the same settings, in the
+        order of the lists as given; ``status`` / ``n_steps`` / ``Y`` (``want_Y``) are bit-equal to ``simulate_batch``'s.  ``metric`` is
+        "total_signal", "mean", "variance" or "l2_norm"; a flagged candidate has metric NaN and an all-NaN pred row; a candidate's value
+        does not depend on the batch around it.  ``method`` / ``kernel`` / ``rtol`` / ``atol`` as in ``simulate_batch``.  ``None`` when the
+        launch is refused (``pk_network_simulate_measure_batch`` answers PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy): it runs
+        where the plan is the order-3 method on the general LDS kernel or the HBM-workspace kernel -- by default on networks beyond one
+        workgroup, elsewhere with ``method="rosw", kernel="lds"`` (or ``kernel="workspace"``) -- and for lists whose protein / phospho
+        baselines are time index 0 with no rna observation before the rna baseline."""
+        if method not in ("auto", "ark", "rosw", "dp5"):
+            raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
+        if kernel not in ("auto", "lds", "workspace"):
+            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
+        if metric not in _capi.NET_METRICS:
+            raise ValueError(f"metric must be one of {sorted(_capi.NET_METRICS)}")
+        if lists not in self._n_obs:
+            raise ValueError("lists must be a handle made by this engine's make_index_lists / make_loss (and not freed)")
+        if rtol is None or atol is None:
+            try:
+                ark = self.resolved_method(method, kernel) == "ark"      # such a plan is refused below; the defaults only have to be valid
+            except _capi.PhoskinError:
+                return None
+            rtol = (1e-8 if ark else 1e-7) if rtol is None else rtol
+            atol = (1e-8 if ark else 1e-9) if atol is None else atol
+        dev = torch.device("cuda", self.ctx.device)
+        xd = _dev_f64(x, dev)
+        if xd.dim() == 1:
+            xd = xd.unsqueeze(0)
+        if xd.shape[1] != self.n_var:
+            raise ValueError(f"x must be [B, {self.n_var}]")
+        B = xd.shape[0]
+        yd = _dev_f64(self.default_y0() if y0 is None else y0, dev)
+        if yd.shape == (self.S,):
+            yb = 0
+        elif yd.shape == (B, self.S):
+            yb = 1
+        else:
+            raise ValueError(f"y0 must be [{self.S}] or [{B}, {self.S}]")
+        th = np.ascontiguousarray(np.atleast_1d(np.asarray(t_eval, dtype=np.float64)))
+        T = th.size
+        Y = torch.empty((B, T, self.S), dtype=torch.float64, device=dev) if want_Y else None
+        pred = torch.empty((B, self._n_obs[lists]), dtype=torch.float64, device=dev) if want_pred else None
+        val = torch.empty((B,), dtype=torch.float64, device=dev)
+        status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        nsteps = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+        opts = self._opts(method, kernel, rtol=rtol, atol=atol, max_steps=max_steps)
+        self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self.ctx.lib.pk_network_simulate_measure_batch(self.ctx.handle, self._h, lists, B, _ptr(xd), int(raw), _ptr(yd), yb, th.ctypes.data, T,
+                                                            C.byref(opts), float(eps), _capi.NET_METRICS[metric], _ptr(Y), _ptr(pred), _ptr(val),
+                                                            _ptr(status), _ptr(nsteps))
+        if rc == _capi.PK_ERR_UNSUPPORTED:
+            return None
+        self.ctx.check(rc)
+        val._keepalive = (xd, yd)  # type: ignore[attr-defined]
+        return val, pred, status, nsteps, Y
+
     def resolved_method(self, method: str = "auto", kernel: str = "auto") -> str:
         """The integrator ``simulate_batch(method=, kernel=)`` will run on this network -- "ark", "rosw" or "dp5" -- as decided by the
         library itself (``pk_network_resolve_method``: network size, sites per protein AND the LDS footprint of the order-4 kernel).
@@ -285,9 +348,11 @@ class NetworkEngine:
         h = self.ctx.lib.pk_network_loss_create(self.ctx.handle, self._h, C.byref(d), int(T))
         if not h:
             raise _capi.PhoskinError("pk_network_loss_create failed: " + (self.ctx.lib.pk_last_error(self.ctx.handle) or b"").decode())
+        self._n_obs[h] = int(keep["p_prot"].size + keep["p_rna"].size + keep["p_pho"].size)
         return h
 
     def free_loss(self, h):
+        self._n_obs.pop(h, None)
         self.ctx.lib.pk_network_loss_destroy(h)
 
     def objective_batch(self, loss, Y: torch.Tensor, loss_mode: int = 0, x=None, raw: bool = False, defaults=None,

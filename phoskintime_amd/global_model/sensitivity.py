@@ -92,13 +92,18 @@ def run_sensitivity_batch(eng: NetworkEngine, fitted_params: Dict, times_p, time
                           trajectories: int = config.SENSITIVITY_TRAJECTORIES, num_levels: int = config.SENSITIVITY_LEVELS,
                           metric: str = config.SENSITIVITY_METRIC, seed: Optional[int] = None,
                           param_values: Optional[np.ndarray] = None, y0=None, conf_level: float = 0.95, rtol: Optional[float] = None, atol: Optional[float] = None,
-                          vary=None, return_pred: bool = False):
+                          vary=None, return_pred: bool = False, fused: bool = False, method: str = "auto", kernel: str = "auto"):
     """Returns dict(Si, problem, param_values, Y, status).  ``fitted_params`` maps the eight parameter groups (System.update order)
     to arrays / a scalar; every entry is varied, as in the reference (sensitivity.py:196-215) -- unless ``vary`` names a subset: indices
     into the flat parameter vector (or parameter names ``"A_i_3"``, ``"tf_scale"``); the design then has len(vary) dimensions
     (trajectories x (len(vary) + 1) simulations: BASELINE config 4 is 128 x (200 + 1)) and every other entry stays at its fitted value.
     ``param_values`` (a ready sample matrix) has one column per varied entry.  ``return_pred``: also return the fold-change observables
-    ``pred`` [rows of this rank, n_obs] (GPU tensor) and their ``layout``."""
+    ``pred`` [rows of this rank, n_obs] (GPU tensor) and their ``layout``.  ``method`` / ``kernel`` go to ``simulate_batch``.
+    ``fused=True``: one ``simulate_measure_batch`` launch measures and reduces every row inside the integrator instead of the three steps
+    simulate -> observables -> metric, so neither the trajectories [rows, T, S] nor (without ``return_pred``) the observables
+    [rows, n_obs] are allocated; it integrates with the order-3 method -- ``method="rosw"``, ``kernel="lds"`` unless the caller names one
+    (the library moves to the workspace kernel where the LDS kernel does not fit) -- so compare it with the unfused call at those settings.
+    ``metric`` must then be one of the four named metrics; a refused launch raises ``PhoskinError`` with the library's reason."""
     params = {k: (np.asarray(fitted_params[k], float) if k != "tf_scale" else float(fitted_params[k])) for k in _ORDER}
     from .simulate import measure_tolerances                  # the settings of simulate_and_measure, which the reference's workers call
     tol = measure_tolerances(eng)
@@ -142,10 +147,21 @@ def run_sensitivity_batch(eng: NetworkEngine, fitted_params: Dict, times_p, time
     mean_steps = None
     try:
         if rows.numel() > 0:
-            Y, status, nst = eng.simulate_batch(Xd if world == 1 else Xd[rows], times, y0=y0, rtol=rtol, atol=atol, max_steps=5000 * times.size)
+            Xloc = Xd if world == 1 else Xd[rows]
+            if fused:
+                out = eng.simulate_measure_batch(lists, Xloc, times, y0=y0, rtol=rtol, atol=atol, max_steps=5000 * times.size, metric=metric, eps=1e-12,
+                                                 want_pred=return_pred, method=("rosw" if method == "auto" else method),
+                                                 kernel=("lds" if kernel == "auto" else kernel))
+                if out is None:
+                    from .. import _capi
+                    raise _capi.PhoskinError("run_sensitivity_batch(fused=True): the fused launch was refused: "
+                                             + (eng.ctx.lib.pk_last_error(eng.ctx.handle) or b"").decode() + " -- or call with fused=False")
+                yloc, pred, status, nst, _ = out
+            else:
+                Y, status, nst = eng.simulate_batch(Xloc, times, y0=y0, rtol=rtol, atol=atol, max_steps=5000 * times.size, method=method, kernel=kernel)
+                pred = eng.observables_batch(lists, Y, n_obs, eps=1e-12)
+                yloc = scalar_metric_batch(pred, metric)
             mean_steps = nst.double().mean(dim=0)
-            pred = eng.observables_batch(lists, Y, n_obs, eps=1e-12)
-            yloc = scalar_metric_batch(pred, metric)
             yloc = torch.where(status != 0, torch.zeros_like(yloc), yloc)          # failed simulations contribute Y = 0
         else:
             dev = torch.device("cuda", eng.ctx.device)
@@ -182,7 +198,7 @@ def _worker_simulation(task_args):
 
 
 def run_sensitivity_analysis(sys, idx, fitted_params, output_dir, metric="total_signal", seed: Optional[int] = None,
-                             param_values: Optional[np.ndarray] = None):
+                             param_values: Optional[np.ndarray] = None, fused: bool = False):
     """Morris screening of the network around ``fitted_params`` with the reference's argument list (sensitivity.py:171-297) -> the
     DataFrame ``Parameter, mu_star, sigma, mu_star_conf`` sorted by influence, also written to ``<output_dir>/sensitivity_indices.csv``.
 
@@ -191,7 +207,8 @@ def run_sensitivity_analysis(sys, idx, fitted_params, output_dir, metric="total_
     task of a process pool); under an initialised ``torch.distributed`` group the rows are sharded over the ranks with one all-gather of Y.
     ``<output_dir>/sensitivity_trajectories.csv`` lists the ``config.SENSITIVITY_TOP_CURVES`` samples of largest Y (id, y_val and the
     sampled parameter values; the reference stores whole DataFrames in that table's cells).  The two plots (:290-296) are not drawn.
-    ``seed`` defaults to ``config.SEED``; ``param_values`` (keyword, not in the reference) takes a ready sample matrix such as SALib's."""
+    ``seed`` defaults to ``config.SEED``; ``param_values`` (keyword, not in the reference) takes a ready sample matrix such as SALib's;
+    ``fused`` (keyword, not in the reference) is ``run_sensitivity_batch``'s: measure and reduce inside the integrator."""
     import os
     import pandas as pd
     from .simulate import engine_for
@@ -202,7 +219,8 @@ def run_sensitivity_analysis(sys, idx, fitted_params, output_dir, metric="total_
         params[k] = float(v) if k == "tf_scale" else np.asarray(v, dtype=float)
     res = run_sensitivity_batch(eng, params, config.TIME_POINTS_PROTEIN, config.TIME_POINTS_RNA, config.TIME_POINTS_PHOSPHO, metric=metric,
                                 perturbation=config.SENSITIVITY_PERTURBATION, trajectories=config.SENSITIVITY_TRAJECTORIES,
-                                num_levels=config.SENSITIVITY_LEVELS, seed=config.SEED if seed is None else seed, param_values=param_values, y0=np.asarray(sys.y0(), dtype=np.float64))
+                                num_levels=config.SENSITIVITY_LEVELS, seed=config.SEED if seed is None else seed, param_values=param_values, y0=np.asarray(sys.y0(), dtype=np.float64),
+                                fused=fused)
     Si = res["Si"]
     df_sens = pd.DataFrame({"Parameter": res["problem"]["names"], "mu_star": Si["mu_star"], "sigma": Si["sigma"], "mu_star_conf": Si["mu_star_conf"]})
     df_sens = df_sens.sort_values("mu_star", ascending=False)
