@@ -8,7 +8,10 @@
 //   * a replica is owned by G lanes (G = 4, 8 or 16), each lane holding RPL site rows in registers
 //     (site i = lane + G * j), so S = 32 runs EIGHT replicas per wavefront instead of two;
 //   * the two coupling rows (mRNA R and unphosphorylated protein P) are "shadowed": every lane of the group carries
-//     them as wave-uniform-per-group scalars and updates them redundantly, so no broadcast is ever needed;
+//     them and updates them redundantly, so no broadcast is ever needed.  The copies agree to rounding, not to the bit: each lane
+//     inverts 1 + q B in a chain with its own site pivots (factor(), below), so the lanes' R and P drift a few ulps apart (4.7e-14
+//     relative at most in the CPU model, tools/pivot_chain_sensitivity.py).  Everything that steers a replica -- the error norm, the
+//     site sum, the non-finite test -- is reduced over the group and so uniform; lane 0 emits R and P;
 //   * the site sum that closes row P is needed once per step (by the right-hand side of the accepted state), so it is formed once per
 //     step: a tree over the candidate's site rows in the lane, then one group reduction, taken over under the accept predicate.  A
 //     stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
@@ -334,13 +337,41 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 
   // Arrow factors of M = I - q J (q = gamma h) for the current step size.
   //   rows: (1 + q B) x_R = r_R ; (1 + q d_i) x_i - q S_i x_P = r_i ; (1 + q Dsum) x_P - q C x_R - q sum x_i = r_P
+  // The RPL + 1 pivots 1 + q B and 1 + q d_j of a lane do not depend on each other and are inverted through shared reciprocals
+  // (chain_rcp, pk_linsolve.hpp): one chain while there are at most five of them, two chains split as evenly as possible above that
+  // ({B, rows 0-3} and {rows 4-7} at 8 rows), which halves the dependent latency and keeps every product at five pivots or fewer.
+  // A replica is solved while the product of the pivots of each chain is finite (pivots up to about 1e61 each; the parent asked only
+  // that each pivot be finite), and a zero or non-finite pivot spoils its chain at once where it reached the group sum one solve later.
+  // sinv depends on all of them and keeps its own reciprocal.
   double winv[RPL], cw[RPL], winvR, sinv, Scw, qq;
   auto factor = [&](const double q) {
     qq = q;
-    winvR = fast_rcp(__builtin_fma(q, cB, 1.0));
+    constexpr int NP = RPL + 1, M0 = NP <= 5 ? NP : (NP + 1) / 2, M1 = NP - M0;
+    double piv[NP];
+    piv[0] = __builtin_fma(q, cB, 1.0);
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      winv[j] = fast_rcp(__builtin_fma(q, pk.template get<K_DG + j>(), 1.0));
+      piv[1 + j] = __builtin_fma(q, pk.template get<K_DG + j>(), 1.0);
+    });
+    {
+      double a[M0], inv[M0];
+#pragma unroll
+      for (int i = 0; i < M0; ++i) a[i] = piv[i];
+      chain_rcp<M0>(a, inv);
+      winvR = inv[0];
+#pragma unroll
+      for (int i = 1; i < M0; ++i) winv[i - 1] = inv[i];
+    }
+    if constexpr (M1 > 0) {
+      double a[M1], inv[M1];
+#pragma unroll
+      for (int i = 0; i < M1; ++i) a[i] = piv[M0 + i];
+      chain_rcp<M1>(a, inv);
+#pragma unroll
+      for (int i = 0; i < M1; ++i) winv[M0 - 1 + i] = inv[i];
+    }
+    static_for<RPL>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
       cw[j] = q * pk.template get<K_SR + j>() * winv[j];
     });
     Scw = gsum<G>(tree_sum(cw), lane);

@@ -18,6 +18,27 @@ __device__ __forceinline__ double fast_rcp(double x) {
   return r;
 }
 
+// The M reciprocals 1 / a[i] from ONE fast_rcp (of the product of the factors) and 3 (M - 1) plain multiplies:
+//   p_0 = a_0, p_i = p_{i-1} a_i ;  r = fast_rcp(p_{M-1}) ;  for i = M - 1 .. 1: inv_i = r p_{i-1}, r = r a_i ;  inv_0 = r.
+// The sequence is fixed (results depend on it to the bit): no re-association, no refinement per element.  Each inv_i carries up to
+// 2 (M - 1) roundings around the refined reciprocal: relative error under 2 (M + 1) 2^-53.  What it asks of the factors: their PRODUCT
+// must be normal and finite, not only each of them (five factors of 1e61 each still are; one factor of 1e200 beside ordinary ones is),
+// and a zero, inf or NaN factor spoils every reciprocal of the chain.
+template <int M>
+__device__ __forceinline__ void chain_rcp(const double (&a)[M], double (&inv)[M]) {
+  double p[M];
+  p[0] = a[0];
+#pragma unroll
+  for (int i = 1; i < M; ++i) p[i] = p[i - 1] * a[i];
+  double r = fast_rcp(p[M - 1]);
+#pragma unroll
+  for (int i = M - 1; i >= 1; --i) {
+    inv[i] = r * p[i - 1];
+    r = r * a[i];
+  }
+  inv[0] = r;
+}
+
 // 1/x from v_rcp_f64 alone (relative error ~1e-8): for quantities that only steer the step-size controller (error ratios), where one
 // instruction instead of seven is worth more than the last eight digits
 __device__ __forceinline__ double approx_rcp(double x) { return __builtin_amdgcn_rcp(x); }
