@@ -7,11 +7,16 @@
 //
 //   * a replica is owned by G lanes (G = 4, 8 or 16), each lane holding RPL site rows in registers
 //     (site i = lane + G * j), so S = 32 runs EIGHT replicas per wavefront instead of two;
-//   * the two coupling rows (mRNA R and unphosphorylated protein P) are "shadowed": every lane of the group carries
+//   * SHADOWED layout (RES = false: every size of the RODAS4 / LRP8 table, and the LRP12 sizes whose lane layout has no two spare
+//     slots): the two coupling rows (mRNA R and unphosphorylated protein P) are "shadowed": every lane of the group carries
 //     them and updates them redundantly, so no broadcast is ever needed.  The copies agree to rounding, not to the bit: each lane
 //     inverts 1 + q B in a chain with its own site pivots (factor(), below), so the lanes' R and P drift a few ulps apart (4.7e-14
 //     relative at most in the CPU model, tools/pivot_chain_sensitivity.py).  Everything that steers a replica -- the error norm, the
 //     site sum, the non-finite test -- is reduced over the group and so uniform; lane 0 emits R and P;
+//   * RESIDENT layout (RES = true: the LRP12 sizes with G * RPL >= n + 2, the benchmark's n = 30 on 4 x 8 among them): R and P ride in
+//     slots 0 and 1 of the lane layout as rows of lanes 0 and 1, the sites follow in state order.  There is ONE copy of each (nothing to
+//     agree or drift), no lane pushes a redundant R / P through the stages, and no row is idle at n + 2 = G * RPL; the price is two
+//     broadcasts per step (R and P for the right-hand side).  Described at the kernel, below;
 //   * the site sum that closes row P is needed once per step (by the right-hand side of the accepted state), so it is formed once per
 //     step: a tree over the candidate's site rows in the lane, then one group reduction, taken over under the accept predicate.  A
 //     stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
@@ -23,29 +28,35 @@
 
 namespace pk {
 
-template <int RPL>
+template <int RPL, bool RES = false>
 struct Stg {               // one vector of the system as seen by a lane: a stage, a candidate, an error estimate
   double s[RPL];           // this lane's site rows
   double R, P;             // shadow rows (identical in every lane of the group)
 };
 template <int RPL>
-struct Trk : Stg<RPL> {    // the accepted state: the only vector whose site sum is read (by the right-hand side, once per step)
+struct Stg<RPL, true> {    // resident layout: R and P are rows like any other (slot 0 and slot 1), nothing is shadowed
+  double s[RPL];           // this lane's slots: state lane + G * j
+};
+template <int RPL, bool RES = false>
+struct Trk : Stg<RPL, RES> {    // the accepted state: the only vector whose site sum is read (by the right-hand side, once per step)
   double sg;               // sum over ALL sites of the group (identical in every lane): site_sum of the rows above, nothing else
 };
 
-template <int RPL>
-__device__ __forceinline__ void trk_axpy(Stg<RPL>& acc, const double a, const Stg<RPL>& u) {
+template <int RPL, bool RES>
+__device__ __forceinline__ void trk_axpy(Stg<RPL, RES>& acc, const double a, const Stg<RPL, RES>& u) {
 #pragma unroll
   for (int j = 0; j < RPL; ++j) acc.s[j] = __builtin_fma(a, u.s[j], acc.s[j]);
-  acc.R = __builtin_fma(a, u.R, acc.R);
-  acc.P = __builtin_fma(a, u.P, acc.P);
+  if constexpr (!RES) {
+    acc.R = __builtin_fma(a, u.R, acc.R);
+    acc.P = __builtin_fma(a, u.P, acc.P);
+  }
 }
-template <int RPL>
-__device__ __forceinline__ Stg<RPL> trk_scale(const double a, const Stg<RPL>& u) {
-  Stg<RPL> r;
+template <int RPL, bool RES>
+__device__ __forceinline__ Stg<RPL, RES> trk_scale(const double a, const Stg<RPL, RES>& u) {
+  Stg<RPL, RES> r;
 #pragma unroll
   for (int j = 0; j < RPL; ++j) r.s[j] = a * u.s[j];
-  r.R = a * u.R; r.P = a * u.P;
+  if constexpr (!RES) { r.R = a * u.R; r.P = a * u.P; }
   return r;
 }
 // the sum over all sites of a replica: a tree over the lane's rows, then the group reduction (every y.sg of the kernel is this function
@@ -93,8 +104,10 @@ using DistSolOnly = DistFixed<true, false, false, true, PK_DM_NONE>;
 using DistFlatOnly = DistFixed<true, false, true, false, PK_DM_NONE>;
 
 // number of per-lane slots: site rates S_i and 1 + D_i always; the running sum from PK_DM_SUM on; previous outputs, second moment, first
-// differences and shift only in PK_DM_FULL
-template <int RPL, int MC> constexpr int dist_fast_slots() { return MC == PK_DM_FULL ? 3 * RPL + 6 : MC == PK_DM_SUM ? 2 * RPL + 1 : 2 * RPL; }
+// differences and shift only in PK_DM_FULL (the resident layout has no previous R / P beside the previous outputs of its slots: two fewer)
+template <int RPL, int MC, bool RES = false> constexpr int dist_fast_slots() {
+  return MC == PK_DM_FULL ? 3 * RPL + (RES ? 4 : 6) : MC == PK_DM_SUM ? 2 * RPL + 1 : 2 * RPL;
+}
 
 // Per-lane values that are touched once per step (site rates) or once per output (metric bookkeeping).  In registers by default;
 // PARK = true keeps them in LDS (slot-major: slot * NT + thread, conflict-free), which frees up to 6 * RPL + 12 VGPRs: what lets the
@@ -118,23 +131,35 @@ template <int RPL, int NT> struct Parked<RPL, true, NT> {
   __device__ __forceinline__ void fence() { asm volatile("" : "+v"(base)); }
 };
 // the parked layouts keep the site rows of the accepted state in RPL more slots (the step loop reads them at the top of a step, accepting lanes write them)
-template <int RPL, bool PARK, int NT = 256, class CFG = DistAny>
-constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<RPL, CFG::SLOT_MC>() + RPL) * NT * sizeof(double) : 0; }
+template <int RPL, bool PARK, int NT = 256, class CFG = DistAny, bool RES = false>
+constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<RPL, CFG::SLOT_MC, RES>() + RPL) * NT * sizeof(double) : 0; }
 
 // NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
-template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny>
+//
+// RES = true is the RESIDENT layout, for sizes whose whole state fits the lane layout (G * RPL >= n + 2): the state vector is laid over
+// the G x RPL slots in state order, slot s = lane + G * row holding state s -- R in slot 0 (lane 0, row 0), P in slot 1 (lane 1, row 0),
+// site i in slot i + 2, slots >= n + 2 idle (rate 0, diagonal 1, value 0).  Nothing is shadowed: R and P go through the stages, the
+// error norm, the parked K_Y slots and a landing as rows of their lanes, and only row 0 ever differs between the lanes of a group:
+//   * solve: R is a row with pivot 1 + q B and no coupling; the P slot's "pivot" is q itself, so that its t is r_P / q and the ONE group
+//     sum  C x_R + r_P / q + sum t_i  (row 0 enters with the per-lane weight w0 = C, 1, 1, ...) times q sinv is x_P;
+//   * right-hand side: R and P are broadcast from their lanes once per step; row 0 is fma(k1, P, fma(-dg0, X, k3)) with per-lane
+//     k1 = 0 | -Dsum | S_i, dg0 = B | -C | 1 + D_i, X = R | R | x_i, k3 = A | sg | 0  (lane 0 | lane 1 | the others);
+//   * the site sum skips the R and P slots; every reduction that steers a replica is still a group reduction.
+template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny, bool RES = false>
 __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) {
   using Tab = ResolventTab<METHOD>;
+  using Vec = Stg<RPL, RES>;
   extern __shared__ __align__(16) double park_lds[];
   Parked<RPL, PARK, NT> pk(park_lds);
   // the parked slots of every wave the launch bounds promise a CU (4 SIMDs x MINB) must fit its 160 KiB; the tightest entry of the launch
   // tables is DistAny at 8 rows: 38 slots x 512 B x 8 waves = 152 KiB, so three more slots per thread would not fit there
-  static_assert(dist_fast_lds_bytes<RPL, PARK, 64, CFG>() * 4 * MINB <= 160 * 1024, "parked slots exceed the CU's LDS at this occupancy");
+  static_assert(dist_fast_lds_bytes<RPL, PARK, 64, CFG, RES>() * 4 * MINB <= 160 * 1024, "parked slots exceed the CU's LDS at this occupancy");
   // slots: [0, RPL) S_i ; [RPL, 2 RPL) 1 + D_i ; then m1 (PK_DM_SUM), or previous site outputs, prevR, prevP, m1, m2, mdyn, shift (PK_DM_FULL);
-  // PARK only: [K_Y, K_Y + RPL) the site rows of the last accepted state
+  // PARK only: [K_Y, K_Y + RPL) the site rows of the last accepted state.  Resident: no prevR / prevP; the rows are the lane's slots
   constexpr int MCS = CFG::SLOT_MC;
-  constexpr int K_SR = 0, K_DG = RPL, K_PS = 2 * RPL, K_PR = 3 * RPL, K_PP = 3 * RPL + 1, K_M1 = (MCS == PK_DM_FULL ? 3 * RPL + 2 : 2 * RPL),
-                K_M2 = 3 * RPL + 3, K_MD = 3 * RPL + 4, K_SH = 3 * RPL + 5, K_Y = dist_fast_slots<RPL, MCS>();
+  constexpr int NSL = dist_fast_slots<RPL, MCS, RES>(), FB = 3 * RPL + (RES ? 0 : 2);     // FB: first slot after the previous outputs
+  constexpr int K_SR = 0, K_DG = RPL, K_PS = 2 * RPL, K_PR = 3 * RPL, K_PP = 3 * RPL + 1, K_M1 = (MCS == PK_DM_FULL ? FB : 2 * RPL),
+                K_M2 = FB + 1, K_MD = FB + 2, K_SH = FB + 3, K_Y = NSL;
   constexpr int RPB = NT / G;
   const int lane = lane_id();
   const int l = threadIdx.x & (G - 1);
@@ -145,38 +170,54 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   const double* __restrict__ th = A.theta + rep * A.P;
 
   // ---- coefficients: uniform (A, B, C, D + sum S) and per site (S_i, 1 + D_i); padding sites are inert (S = 0, d = 1)
+  // Resident: the R and P slots have rate 0 (they add nothing to Dsum and Scw); their diagonal slots carry B (pivot 1 + q B) and -C
+  // (the P slot has no pivot of this form: factor() puts q in its place), and the three per-lane values of row 0 are kept beside them:
+  // w0 (weight of row 0 in the group sum of a solve), k3 (the constant of row 0's right-hand side), both 1 / 0 in a site lane
   const double cA = th[0], cB = th[1], cC = th[2];
+  const bool isR = RES && l == 0, isP = RES && l == 1;
+  const double w0 = isR ? cC : 1.0, k3 = isR ? cA : 0.0;
   double lsum = 0.0;
   static_for<RPL>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
-    const int i = l + G * j;
-    const bool ok = i < n;
+    const int i = l + G * j - (RES ? 2 : 0);
+    const bool ok = i >= 0 && i < n;
     const double sr = ok ? th[4 + i] : 0.0;
+    double dg = ok ? 1.0 + th[4 + n + i] : 1.0;
+    if constexpr (RES && j == 0) dg = isR ? cB : isP ? -cC : dg;
     pk.template set<K_SR + j>(sr);
-    pk.template set<K_DG + j>(ok ? 1.0 + th[4 + n + i] : 1.0);
+    pk.template set<K_DG + j>(dg);
     lsum += sr;
   });
   const double Dsum = th[3] + gsum<G>(lsum, lane);
+  // the sum over the site slots of a resident lane: row 0 of lanes 0 and 1 (R and P) stays out
+  auto sites_only = [&](const double (&s)[RPL]) {
+    double v[RPL];
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) v[j] = s[j];
+    v[0] = (isR || isP) ? 0.0 : v[0];
+    return gsum<G>(tree_sum(v), lane);
+  };
 
   // ---- state
   const double* y0p = A.y0 + (A.y0_batched ? rep * S : 0);
-  Trk<RPL> y;
-  y.R = y0p[0]; y.P = y0p[1];
+  Trk<RPL, RES> y;
+  if constexpr (!RES) { y.R = y0p[0]; y.P = y0p[1]; }
 #pragma unroll
   for (int j = 0; j < RPL; ++j) {
     const int i = l + G * j;
-    y.s[j] = (i < n) ? y0p[2 + i] : 0.0;
+    if constexpr (RES) y.s[j] = (i < S) ? y0p[i] : 0.0;
+    else y.s[j] = (i < n) ? y0p[2 + i] : 0.0;
   }
-  y.sg = site_sum<G>(y.s, lane);
+  if constexpr (RES) y.sg = sites_only(y.s); else y.sg = site_sum<G>(y.s, lane);
   if constexpr (PARK) static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(y.s[j]); });
 
   // ---- output / fused Morris metric (same semantics as Emitter in pk_solve_kernel.hpp)
-  static_for<dist_fast_slots<RPL, MCS>() - 2 * RPL>([&](auto kc) { pk.template set<K_PS + decltype(kc)::value>(0.0); });
+  static_for<NSL - 2 * RPL>([&](auto kc) { pk.template set<K_PS + decltype(kc)::value>(0.0); });
   const int T5 = T > 5 ? T - 5 : 0;
-  // this lane's first site in the trajectory row of the next output time; advanced by one row per landing
-  double* srow = CFG::sol(A) ? A.sol + rep * T * S + 2 + l : nullptr;
+  // this lane's first site (resident: first slot) in the trajectory row of the next output time; advanced by one row per landing
+  double* srow = CFG::sol(A) ? A.sol + rep * T * S + (RES ? 0 : 2) + l : nullptr;
   // one output row: nf = std::true_type writes the NaN rows of a failed replica (cold), std::false_type the values of v
-  auto emit = [&](const int k, const Stg<RPL>& v, auto nf) {
+  auto emit = [&](const int k, const Vec& v, auto nf) {
     constexpr bool nan_fill = decltype(nf)::value;
     double* fl = CFG::flat(A) ? A.flat + rep * A.F : nullptr;
     // The clip `x < 0 ? 0 : x` (a compare and two selects per double) changes a value only where its sign bit is set: x < 0 is false for
@@ -186,7 +227,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     bool clip_now = CFG::clip(A);
     if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
       typedef int dwords __attribute__((ext_vector_type(2)));      // element 1 = the high dword; as a shift of the 64 bits the OR is done on both dwords
-      int sgn = __builtin_bit_cast(dwords, v.R).y | __builtin_bit_cast(dwords, v.P).y;
+      int sgn = 0;
+      if constexpr (!RES) sgn = __builtin_bit_cast(dwords, v.R).y | __builtin_bit_cast(dwords, v.P).y;
 #pragma unroll
       for (int j = 0; j < RPL; ++j) sgn |= __builtin_bit_cast(dwords, v.s[j]).y;
       clip_now = __builtin_amdgcn_ballot_w64(sgn < 0) != 0;
@@ -197,17 +239,21 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       if (CFG::normalize(A)) r *= 1.0 / y0p[state];
       return r;
     };
-    Stg<RPL> c = v;                                     // the clipped state
+    Vec c = v;                                          // the clipped state
     if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
-      asm volatile("" : "+v"(c.R));                     // keeps this a branch: without it the compiler folds the test into each select
-      c.R = (c.R < 0.0) ? 0.0 : c.R; c.P = (c.P < 0.0) ? 0.0 : c.P;
+      // keeps this a branch: without it the compiler folds the test into each select
+      if constexpr (RES) asm volatile("" : "+v"(c.s[0])); else asm volatile("" : "+v"(c.R));
+      if constexpr (!RES) { c.R = (c.R < 0.0) ? 0.0 : c.R; c.P = (c.P < 0.0) ? 0.0 : c.P; }
 #pragma unroll
       for (int j = 0; j < RPL; ++j) c.s[j] = (c.s[j] < 0.0) ? 0.0 : c.s[j];
     }
-    const double vR = val(c.R, 0), vP = val(c.P, 1);
-    if (l == 0) {
-      if (CFG::sol(A)) { srow[-2] = vR; srow[-1] = vP; }
-      if (CFG::flat(A)) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
+    double vR = 0.0, vP = 0.0;
+    if constexpr (!RES) {
+      vR = val(c.R, 0); vP = val(c.P, 1);
+      if (l == 0) {
+        if (CFG::sol(A)) { srow[-2] = vR; srow[-1] = vP; }
+        if (CFG::flat(A)) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
+      }
     }
     // An idle row (i >= n: rate 0, initial value 0) holds +0 or -0 in every accepted state -- each of its stage values is
     // fma(0, x_P, +-0) with x_P finite -- so its clipped value is a zero already.  Adding a zero of either sign instead of +0.0 can
@@ -215,14 +261,25 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     // to the same bits.  Only normalize (which would read y0 past its end) still needs the mask; the run-time kernel keeps it.
     const bool masked = CFG::LITERAL || CFG::normalize(A);
     double vs[RPL];
-    double loc = (l == 0) ? vR + vP : 0.0;
+    // Resident: every lane stores its slots, no lane-0 branch.  Slot s of the flat vector is at T5 + (s - 1) T + k for every s: the
+    // sites from T5 + T on, P (s = 1) at T5 + k, and R (s = 0) at k - 5 when T > 5 (T5 = T - 5) -- stored from k = 5 on, and never
+    // when T <= 5 (k < T).  The running sum is the plain sum of the lane's emitted values.
+    double loc = (!RES && l == 0) ? vR + vP : 0.0;
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
       const int i = l + G * j;
-      vs[j] = (i < n || !masked) ? val(c.s[j], 2 + i) : 0.0;
-      if (i < n) {
-        if (CFG::sol(A)) srow[G * j] = vs[j];
-        if (CFG::flat(A)) fl[T5 + T + i * T + k] = vs[j];
+      if constexpr (RES) {
+        vs[j] = (i < S || !masked) ? val(c.s[j], i) : 0.0;
+        if (i < S) {
+          if (CFG::sol(A)) srow[G * j] = vs[j];
+          if (CFG::flat(A)) if (j > 0 || i > 0 || k >= 5) fl[T5 + (i - 1) * T + k] = vs[j];
+        }
+      } else {
+        vs[j] = (i < n || !masked) ? val(c.s[j], 2 + i) : 0.0;
+        if (i < n) {
+          if (CFG::sol(A)) srow[G * j] = vs[j];
+          if (CFG::flat(A)) fl[T5 + T + i * T + k] = vs[j];
+        }
       }
       loc += vs[j];
     }
@@ -233,7 +290,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       pk.template set<K_M1>(pk.template get<K_M1>() + loc);
       if constexpr (MCS == PK_DM_FULL) if (mclass == PK_DM_FULL) {
         double m2 = pk.template get<K_M2>(), mdyn = pk.template get<K_MD>(), shift = pk.template get<K_SH>();
-        double prevR = pk.template get<K_PR>(), prevP = pk.template get<K_PP>();
+        double prevR = 0.0, prevP = 0.0;
+        if constexpr (!RES) { prevR = pk.template get<K_PR>(); prevP = pk.template get<K_PP>(); }
         if (k == 0) {
           shift = gsum<G>(loc, lane) / (2 + n);
           pk.template set<K_SH>(shift);
@@ -243,19 +301,21 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         static_for<RPL>([&](auto jc) {
           constexpr int j = decltype(jc)::value;
           const int i = l + G * j;
-          const double xs = (i < n) ? vs[j] - shift : 0.0;
+          const double xs = (i < (RES ? S : n)) ? vs[j] - shift : 0.0;
           m2 = __builtin_fma(xs, xs, m2);
           const double d = vs[j] - pk.template get<K_PS + j>();
           mdyn = __builtin_fma(d, d, mdyn);
           pk.template set<K_PS + j>(vs[j]);
         });
-        if (l == 0) {
-          const double a = vR - shift, b = vP - shift;
-          m2 = __builtin_fma(a, a, m2); m2 = __builtin_fma(b, b, m2);
-          const double dR = vR - prevR, dP = vP - prevP;
-          mdyn = __builtin_fma(dR, dR, mdyn); mdyn = __builtin_fma(dP, dP, mdyn);
+        if constexpr (!RES) {
+          if (l == 0) {
+            const double a = vR - shift, b = vP - shift;
+            m2 = __builtin_fma(a, a, m2); m2 = __builtin_fma(b, b, m2);
+            const double dR = vR - prevR, dP = vP - prevP;
+            mdyn = __builtin_fma(dR, dR, mdyn); mdyn = __builtin_fma(dP, dP, mdyn);
+          }
+          pk.template set<K_PR>(vR); pk.template set<K_PP>(vP);
         }
-        pk.template set<K_PR>(vR); pk.template set<K_PP>(vP);
         pk.template set<K_M2>(m2); pk.template set<K_MD>(mdyn);
       }
     }
@@ -289,11 +349,12 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   const double rtol = A.rtol, atol = A.atol;
   // max-norm helpers over the whole system (sites of this lane + shadows, then across the group)
   auto q = [&](double e, double ya, double yb) { return fabs(e) * approx_rcp(__builtin_fma(rtol, fmax(fabs(ya), fabs(yb)), atol)); };
-  auto group_max = [&](const Stg<RPL>& num, const Stg<RPL>& a, const Stg<RPL>& b) {   // NaN-propagating: the initial step estimate; DistAny
+  auto group_max = [&](const Vec& num, const Vec& a, const Vec& b) {   // NaN-propagating: the initial step estimate; DistAny
     auto mx = [](double p, double r) { return (p > r || p != p) ? p : r; };
-    double m = mx(q(num.R, a.R, b.R), q(num.P, a.P, b.P));
+    double m;
+    if constexpr (RES) m = q(num.s[0], a.s[0], b.s[0]); else m = mx(q(num.R, a.R, b.R), q(num.P, a.P, b.P));
 #pragma unroll
-    for (int j = 0; j < RPL; ++j) m = mx(m, q(num.s[j], a.s[j], b.s[j]));
+    for (int j = (RES ? 1 : 0); j < RPL; ++j) m = mx(m, q(num.s[j], a.s[j], b.s[j]));
     return gmax<G>(m, lane);
   };
   // The error norm of the step loop: the ratios of group_max for the error estimate e against the accepted state y and the candidate yn,
@@ -301,25 +362,37 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // scale, inf * 0, 0 * inf) is found by unordered compares on pairs of ratios and turned into +inf, which v_max_f64 carries through the
   // group; an inf ratio is the maximum anyway.  The loop treats +inf and NaN alike (reject, then the PK_ST_NONFINITE test), and for finite
   // ratios the maximum has the bits group_max returns.
-  auto err_norm = [&](const Stg<RPL>& e, const Stg<RPL>& y, const Stg<RPL>& yn) {
-    double r[RPL + 2];
-    r[0] = q(e.R, y.R, yn.R); r[1] = q(e.P, y.P, yn.P);
+  auto err_norm = [&](const Vec& e, const Vec& y, const Vec& yn) {
+    constexpr int X = RES ? 0 : 2;                     // resident: the lane's RPL slots are all there is
+    double r[RPL + X];
+    if constexpr (!RES) { r[0] = q(e.R, y.R, yn.R); r[1] = q(e.P, y.P, yn.P); }
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      r[2 + j] = q(e.s[j], y.s[j], yn.s[j]);
+      r[X + j] = q(e.s[j], y.s[j], yn.s[j]);
     });
     double m = tree_max(r);
     if (any_nan(r)) m = __builtin_inf();
     return gmax_num<G>(m, lane);
   };
-  auto rhs_of = [&](const Trk<RPL>& Y) {            // f(Y): the one reader of Y.sg
-    Stg<RPL> f;
-    f.R = __builtin_fma(-cB, Y.R, cA);
-    f.P = __builtin_fma(cC, Y.R, __builtin_fma(-Dsum, Y.P, Y.sg));
-    static_for<RPL>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      f.s[j] = __builtin_fma(pk.template get<K_SR + j>(), Y.P, -pk.template get<K_DG + j>() * Y.s[j]);
-    });
+  auto rhs_of = [&](const Trk<RPL, RES>& Y) {       // f(Y): the one reader of Y.sg
+    Vec f;
+    if constexpr (RES) {
+      // R and P leave their lanes here, once per step.  Row 0: A - B R in lane 0, C R - Dsum P + sg in lane 1, a site row elsewhere
+      const double Rb = bcast<G, 0>(Y.s[0]), Pb = bcast<G, 1>(Y.s[0]);
+      static_for<RPL>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const double sr = pk.template get<K_SR + j>(), dg = pk.template get<K_DG + j>();
+        if constexpr (j == 0) f.s[0] = __builtin_fma(isP ? -Dsum : sr, Pb, __builtin_fma(-dg, isP ? Rb : Y.s[0], isP ? Y.sg : k3));
+        else f.s[j] = __builtin_fma(sr, Pb, -dg * Y.s[j]);
+      });
+    } else {
+      f.R = __builtin_fma(-cB, Y.R, cA);
+      f.P = __builtin_fma(cC, Y.R, __builtin_fma(-Dsum, Y.P, Y.sg));
+      static_for<RPL>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        f.s[j] = __builtin_fma(pk.template get<K_SR + j>(), Y.P, -pk.template get<K_DG + j>() * Y.s[j]);
+      });
+    }
     return f;
   };
 
@@ -328,7 +401,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   double te = A.t[1];
   double h;
   {
-    const Stg<RPL> f0 = rhs_of(y);
+    const Vec f0 = rhs_of(y);
     const double d0 = group_max(y, y, y), d1 = group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
@@ -343,24 +416,31 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // A replica is solved while the product of the pivots of each chain is finite (pivots up to about 1e61 each; the parent asked only
   // that each pivot be finite), and a zero or non-finite pivot spoils its chain at once where it reached the group sum one solve later.
   // sinv depends on all of them and keeps its own reciprocal.
-  double winv[RPL], cw[RPL], winvR, sinv, Scw, qq;
+  // Resident: a lane has RPL pivots, its slots' (same split rule: one chain up to five, two even ones above -- 4 + 4 at 8 rows).  The R
+  // slot's is 1 + q B; the P slot takes q itself as its factor, so the chain of lane 1 hands back 1 / q (what solve() needs to put r_P
+  // into the group sum) and nothing is inverted on its own.  Row 0 enters that sum as r_0 ws0 with ws0 = winv_0 w0 (C / (1 + q B) | 1 / q |
+  // winv_0), and qs = q sinv is the sum's one multiplier.  So that a solve needs no select for the P slot, whose result is x_P itself,
+  // lane 1 ends factor() with winv_0 = 0 and cw_0 = 1: fma(cw_0, x_P, r_P winv_0) is x_P (after Scw, to which the slot adds nothing).
+  double winv[RPL], cw[RPL], winvR, sinv, Scw, qq, qs, ws0;
   auto factor = [&](const double q) {
     qq = q;
-    constexpr int NP = RPL + 1, M0 = NP <= 5 ? NP : (NP + 1) / 2, M1 = NP - M0;
+    constexpr int X = RES ? 0 : 1;
+    constexpr int NP = RPL + X, M0 = NP <= 5 ? NP : (NP + 1) / 2, M1 = NP - M0;
     double piv[NP];
-    piv[0] = __builtin_fma(q, cB, 1.0);
+    if constexpr (!RES) piv[0] = __builtin_fma(q, cB, 1.0);
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      piv[1 + j] = __builtin_fma(q, pk.template get<K_DG + j>(), 1.0);
+      piv[X + j] = __builtin_fma(q, pk.template get<K_DG + j>(), 1.0);
     });
+    if constexpr (RES) piv[0] = isP ? q : piv[0];
     {
       double a[M0], inv[M0];
 #pragma unroll
       for (int i = 0; i < M0; ++i) a[i] = piv[i];
       chain_rcp<M0>(a, inv);
-      winvR = inv[0];
+      if constexpr (!RES) winvR = inv[0];
 #pragma unroll
-      for (int i = 1; i < M0; ++i) winv[i - 1] = inv[i];
+      for (int i = X; i < M0; ++i) winv[i - X] = inv[i];
     }
     if constexpr (M1 > 0) {
       double a[M1], inv[M1];
@@ -368,7 +448,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       for (int i = 0; i < M1; ++i) a[i] = piv[M0 + i];
       chain_rcp<M1>(a, inv);
 #pragma unroll
-      for (int i = 0; i < M1; ++i) winv[M0 - 1 + i] = inv[i];
+      for (int i = 0; i < M1; ++i) winv[M0 - X + i] = inv[i];
     }
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
@@ -376,25 +456,68 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     });
     Scw = gsum<G>(tree_sum(cw), lane);
     sinv = fast_rcp(__builtin_fma(q, Dsum - Scw, 1.0));
+    if constexpr (RES) {
+      qs = q * sinv;
+      ws0 = winv[0] * w0;
+      winv[0] = isP ? 0.0 : winv[0];
+      cw[0] = isP ? 1.0 : cw[0];
+    }
   };
   // u = M^{-1} r: ONE group reduction
-  auto solve = [&](const Stg<RPL>& r) {
-    Stg<RPL> u;
-    const double xR = r.R * winvR;
+  auto solve = [&](const Vec& r) {
+    Vec u;
+    double xR = 0.0;
+    if constexpr (!RES) xR = r.R * winvR;
     double t[RPL];
 #pragma unroll
     for (int j = 0; j < RPL; ++j) t[j] = r.s[j] * winv[j];
-    const double St = gsum<G>(tree_sum(t), lane);
-    const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), r.P) * sinv;
+    if constexpr (RES) {
+      // row 0 adds C x_R in lane 0 and r_P / q in lane 1: the group sum is C x_R + r_P / q + sum t_i, and x_P = sinv (r_P + q (C x_R + sum t_i))
+      double in;
+      if constexpr (RPL > 1) {
+        double rest[RPL - 1];
 #pragma unroll
-    for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
-    u.R = xR; u.P = xP;
+        for (int j = 1; j < RPL; ++j) rest[j - 1] = t[j];
+        in = __builtin_fma(r.s[0], ws0, tree_sum(rest));
+      } else in = r.s[0] * ws0;
+      const double xP = gsum<G>(in, lane) * qs;
+      // uniform over the lanes: cw is 0 in the R slot (x_R = t), and 1 over t = 0 in the P slot (x_P)
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
+    } else {
+      const double St = gsum<G>(tree_sum(t), lane);
+      const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), r.P) * sinv;
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
+      u.R = xR; u.P = xP;
+    }
     return u;
   };
 
   // resolvent-form step (the right-hand side is affine): z_1 = M^{-1} h f(y), z_{k+1} = M^{-1} z_k,
   //   y_new = y + sum_k B_k z_k ,  err = sum_k E_k z_k     (ResolventTab: RODAS4, LRP8 or LRP12)
   bool after_reject = false;
+  // the non-finite test's view of the ACCEPTED state: R, P and the site sum, reduced over the group.  Resident: R and P are row 0 of
+  // lanes 0 and 1 -- in the parked layouts read back from their slots, since y.s holds the candidate from the accept block on
+  auto state_bad = [&]() {
+    bool b;
+    if constexpr (RES) {
+      double r0 = y.s[0];
+      if constexpr (PARK) { pk.fence(); r0 = pk.template get<K_Y>(); }
+      b = ((isR || isP) && nonfinite(r0)) || nonfinite(y.sg);
+    } else b = (nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg));
+    return gmax<G>(b ? 1.0 : 0.0, lane);
+  };
+  // A, B, C of the same test.  Resident: they are not kept in registers through the loop (B and C live in the diagonal slots of lanes 0
+  // and 1, A in lane 0's k3), so this cold path reads them again
+  auto coef_bad = [&]() {
+    if constexpr (RES) {
+      long long r2 = rep;
+      asm volatile("" : "+v"(r2));                        // a fresh address: the prologue's pointer is not kept alive for this
+      const double* t2 = A.theta + r2 * A.P;
+      return (nonfinite(t2[0])) || (nonfinite(t2[1])) || (nonfinite(t2[2]));
+    } else return (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC));
+  };
   // nacc counts the accepted steps.  nsec counts the rejected ones in the run-time kernel and ALL steps in the specialised kernels (one
   // increment per step whatever its fate, and the budget test reads it without an add; finish() gets the difference -- integer, exact)
   int nsec = 0;
@@ -422,9 +545,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       }
       factor(Tab::GAM * hs);
 
-      Stg<RPL> z = solve(trk_scale(hs, rhs_of(y)));
-      Stg<RPL> yn = y; trk_axpy(yn, Tab::B[0], z);
-      Stg<RPL> u6;
+      Vec z = solve(trk_scale(hs, rhs_of(y)));
+      Vec yn = y; trk_axpy(yn, Tab::B[0], z);
+      Vec u6;
       static_for<Tab::NS - 1>([&](auto kc) {
         constexpr int kk = 1 + decltype(kc)::value;
         z = solve(z);
@@ -434,7 +557,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 
       // the candidate's site sum, formed directly (as the C restatement's right-hand side does) and independent of the error norm; an
       // accepting lane takes it over with R and P, a rejecting lane keeps the sum of the state it keeps
-      const double sg_new = site_sum<G>(yn.s, lane);
+      double sg_new;
+      if constexpr (RES) sg_new = sites_only(yn.s); else sg_new = site_sum<G>(yn.s, lane);
       double err;
       if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
       // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
@@ -450,18 +574,18 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         }
 #pragma unroll
         for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
-        y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; y.sg = acc ? sg_new : y.sg;
+        if constexpr (!RES) { y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; }
+        y.sg = acc ? sg_new : y.sg;
       } else {
         if (acc) {
-          static_cast<Stg<RPL>&>(y) = yn; y.sg = sg_new;
+          static_cast<Vec&>(y) = yn; y.sg = sg_new;
           if constexpr (!CFG::LITERAL) tc += hs;
         }
       }
       if constexpr (CFG::LITERAL) {
         if (err != err || err > 1e300) {
           ++nsec; after_reject = true; h = 0.1 * hs;
-          const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
-          if (bad != 0.0 || (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC)) || (nonfinite(Dsum)) || (nonfinite(Scw))) {
+          if (state_bad() != 0.0 || coef_bad() || (nonfinite(Dsum)) || (nonfinite(Scw))) {
             status |= PK_ST_NONFINITE; break;
           }
           continue;
@@ -495,8 +619,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     if (CFG::LITERAL || !nonfin) break;
     // cold: decides exactly as the run-time kernel does in its loop.  y is the accepted state (a NaN or inf error is a rejection), the
     // coefficients never change, and Scw is the one the rejected step's factor() computed -- nothing ran since
-    const double bad = gmax<G>(((nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg))) ? 1.0 : 0.0, lane);
-    if (bad != 0.0 || (nonfinite(cA)) || (nonfinite(cB)) || (nonfinite(cC)) || (nonfinite(Dsum)) || (nonfinite(Scw))) {
+    if (state_bad() != 0.0 || coef_bad() || (nonfinite(Dsum)) || (nonfinite(Scw))) {
       status |= PK_ST_NONFINITE; break;
     }
   }
