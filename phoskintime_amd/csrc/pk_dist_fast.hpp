@@ -15,11 +15,13 @@
 //     site sum, the non-finite test -- is reduced over the group and so uniform; lane 0 emits R and P;
 //   * RESIDENT layout (RES = true: the LRP12 sizes with G * RPL >= n + 2, the benchmark's n = 30 on 4 x 8 among them): R and P ride in
 //     slots 0 and 1 of the lane layout as rows of lanes 0 and 1, the sites follow in state order.  There is ONE copy of each (nothing to
-//     agree or drift), no lane pushes a redundant R / P through the stages, and no row is idle at n + 2 = G * RPL; the price is two
-//     broadcasts per step (R and P for the right-hand side).  Described at the kernel, below;
-//   * the site sum that closes row P is needed once per step (by the right-hand side of the accepted state), so it is formed once per
-//     step: a tree over the candidate's site rows in the lane, then one group reduction, taken over under the accept predicate.  A
-//     stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
+//     agree or drift), no lane pushes a redundant R / P through the stages, and no row is idle at n + 2 = G * RPL.  Described at the
+//     kernel, below;
+//   * the step loop never evaluates the right-hand side: f(y) = J y + b is affine (b = A in row R, zero elsewhere) and J = (I - M) / q,
+//     so the first stage is  M^{-1} h f(y) = (M^{-1} (y + q b) - y) / gamma  -- the same solve() on the state itself with q A added to
+//     row R, then one subtraction per row; 1 / gamma is folded into the tableau weights at compile time.  The site sum that closes
+//     row P, its only reader the right-hand side, is formed in the prologue (initial step estimate) and in the cold non-finite test.
+//     A stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
 //   * no LDS-pipe instruction in the solve chain; LDS only as thread-private parking space in the PARK layouts (below).
 //
 // dR/dt = A - B R ; dP/dt = C R - (D + sum S_i) P + sum X_i ; dX_i/dt = S_i P - (1 + D_i) X_i
@@ -37,11 +39,6 @@ template <int RPL>
 struct Stg<RPL, true> {    // resident layout: R and P are rows like any other (slot 0 and slot 1), nothing is shadowed
   double s[RPL];           // this lane's slots: state lane + G * j
 };
-template <int RPL, bool RES = false>
-struct Trk : Stg<RPL, RES> {    // the accepted state: the only vector whose site sum is read (by the right-hand side, once per step)
-  double sg;               // sum over ALL sites of the group (identical in every lane): site_sum of the rows above, nothing else
-};
-
 template <int RPL, bool RES>
 __device__ __forceinline__ void trk_axpy(Stg<RPL, RES>& acc, const double a, const Stg<RPL, RES>& u) {
 #pragma unroll
@@ -59,8 +56,7 @@ __device__ __forceinline__ Stg<RPL, RES> trk_scale(const double a, const Stg<RPL
   if constexpr (!RES) { r.R = a * u.R; r.P = a * u.P; }
   return r;
 }
-// the sum over all sites of a replica: a tree over the lane's rows, then the group reduction (every y.sg of the kernel is this function
-// of the accepted site rows)
+// the sum over all sites of a replica: a tree over the lane's rows, then the group reduction
 template <int G, int RPL>
 __device__ __forceinline__ double site_sum(const double (&s)[RPL], int lane) { return gsum<G>(tree_sum(s), lane); }
 
@@ -142,8 +138,10 @@ constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<
 // error norm, the parked K_Y slots and a landing as rows of their lanes, and only row 0 ever differs between the lanes of a group:
 //   * solve: R is a row with pivot 1 + q B and no coupling; the P slot's "pivot" is q itself, so that its t is r_P / q and the ONE group
 //     sum  C x_R + r_P / q + sum t_i  (row 0 enters with the per-lane weight w0 = C, 1, 1, ...) times q sinv is x_P;
-//   * right-hand side: R and P are broadcast from their lanes once per step; row 0 is fma(k1, P, fma(-dg0, X, k3)) with per-lane
-//     k1 = 0 | -Dsum | S_i, dg0 = B | -C | 1 + D_i, X = R | R | x_i, k3 = A | sg | 0  (lane 0 | lane 1 | the others);
+//   * first stage: row 0 of the solved vector is fma(q, k3, y_0) with k3 = A | 0 | 0 (lane 0 | lane 1 | the others): y_R + q A in the R
+//     slot, the state itself elsewhere;
+//   * right-hand side (prologue only, for the initial step estimate): R and P are broadcast from their lanes; row 0 is
+//     fma(k1, P, fma(-dg0, X, k3)) with per-lane k1 = 0 | -Dsum | S_i, dg0 = B | -C | 1 + D_i, X = R | R | x_i, k3 = A | sg | 0;
 //   * the site sum skips the R and P slots; every reduction that steers a replica is still a group reduction.
 template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny, bool RES = false>
 __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) {
@@ -200,7 +198,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 
   // ---- state
   const double* y0p = A.y0 + (A.y0_batched ? rep * S : 0);
-  Trk<RPL, RES> y;
+  Vec y;
   if constexpr (!RES) { y.R = y0p[0]; y.P = y0p[1]; }
 #pragma unroll
   for (int j = 0; j < RPL; ++j) {
@@ -208,7 +206,6 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     if constexpr (RES) y.s[j] = (i < S) ? y0p[i] : 0.0;
     else y.s[j] = (i < n) ? y0p[2 + i] : 0.0;
   }
-  if constexpr (RES) y.sg = sites_only(y.s); else y.sg = site_sum<G>(y.s, lane);
   if constexpr (PARK) static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; pk.template set<K_Y + j>(y.s[j]); });
 
   // ---- output / fused Morris metric (same semantics as Emitter in pk_solve_kernel.hpp)
@@ -374,20 +371,20 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     if (any_nan(r)) m = __builtin_inf();
     return gmax_num<G>(m, lane);
   };
-  auto rhs_of = [&](const Trk<RPL, RES>& Y) {       // f(Y): the one reader of Y.sg
+  auto rhs_of = [&](const Vec& Y, const double sg) {       // f(Y) with sg the site sum of Y: the prologue's initial step estimate only
     Vec f;
     if constexpr (RES) {
-      // R and P leave their lanes here, once per step.  Row 0: A - B R in lane 0, C R - Dsum P + sg in lane 1, a site row elsewhere
+      // R and P leave their lanes here.  Row 0: A - B R in lane 0, C R - Dsum P + sg in lane 1, a site row elsewhere
       const double Rb = bcast<G, 0>(Y.s[0]), Pb = bcast<G, 1>(Y.s[0]);
       static_for<RPL>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         const double sr = pk.template get<K_SR + j>(), dg = pk.template get<K_DG + j>();
-        if constexpr (j == 0) f.s[0] = __builtin_fma(isP ? -Dsum : sr, Pb, __builtin_fma(-dg, isP ? Rb : Y.s[0], isP ? Y.sg : k3));
+        if constexpr (j == 0) f.s[0] = __builtin_fma(isP ? -Dsum : sr, Pb, __builtin_fma(-dg, isP ? Rb : Y.s[0], isP ? sg : k3));
         else f.s[j] = __builtin_fma(sr, Pb, -dg * Y.s[j]);
       });
     } else {
       f.R = __builtin_fma(-cB, Y.R, cA);
-      f.P = __builtin_fma(cC, Y.R, __builtin_fma(-Dsum, Y.P, Y.sg));
+      f.P = __builtin_fma(cC, Y.R, __builtin_fma(-Dsum, Y.P, sg));
       static_for<RPL>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         f.s[j] = __builtin_fma(pk.template get<K_SR + j>(), Y.P, -pk.template get<K_DG + j>() * Y.s[j]);
@@ -401,7 +398,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   double te = A.t[1];
   double h;
   {
-    const Vec f0 = rhs_of(y);
+    double sg0;
+    if constexpr (RES) sg0 = sites_only(y.s); else sg0 = site_sum<G>(y.s, lane);
+    const Vec f0 = rhs_of(y, sg0);
     const double d0 = group_max(y, y, y), d1 = group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
@@ -494,18 +493,25 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     return u;
   };
 
-  // resolvent-form step (the right-hand side is affine): z_1 = M^{-1} h f(y), z_{k+1} = M^{-1} z_k,
+  // resolvent-form step (the right-hand side is affine, f(y) = J y + b with b = A in row R): z_1 = M^{-1} h f(y), z_{k+1} = M^{-1} z_k,
   //   y_new = y + sum_k B_k z_k ,  err = sum_k E_k z_k     (ResolventTab: RODAS4, LRP8 or LRP12)
+  // With J = (I - M) / q the first stage needs no right-hand side: gamma z_1 = M^{-1} (y + q b) - y.  The loop carries w_k = gamma z_k
+  // (w_{k+1} = M^{-1} w_k) and the weights B_k / gamma, E_k / gamma, divided at compile time.
   bool after_reject = false;
-  // the non-finite test's view of the ACCEPTED state: R, P and the site sum, reduced over the group.  Resident: R and P are row 0 of
-  // lanes 0 and 1 -- in the parked layouts read back from their slots, since y.s holds the candidate from the accept block on
+  // the non-finite test's view of the ACCEPTED state: R, P and the site sum, reduced over the group.  The step loop carries no site
+  // sum, so this cold path forms it from the accepted rows -- in the parked layouts read back from their slots, since y.s holds the
+  // candidate from the accept block on.  Resident: R and P are row 0 of lanes 0 and 1
   auto state_bad = [&]() {
+    double rows[RPL];
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) rows[j] = y.s[j];
+    if constexpr (PARK) {
+      pk.fence();
+      static_for<RPL>([&](auto jc) { constexpr int j = decltype(jc)::value; rows[j] = pk.template get<K_Y + j>(); });
+    }
     bool b;
-    if constexpr (RES) {
-      double r0 = y.s[0];
-      if constexpr (PARK) { pk.fence(); r0 = pk.template get<K_Y>(); }
-      b = ((isR || isP) && nonfinite(r0)) || nonfinite(y.sg);
-    } else b = (nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(y.sg));
+    if constexpr (RES) b = ((isR || isP) && nonfinite(rows[0])) || nonfinite(sites_only(rows));
+    else b = (nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(site_sum<G>(rows, lane)));
     return gmax<G>(b ? 1.0 : 0.0, lane);
   };
   // A, B, C of the same test.  Resident: they are not kept in registers through the loop (B and C live in the diagonal slots of lanes 0
@@ -545,20 +551,24 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       }
       factor(Tab::GAM * hs);
 
-      Vec z = solve(trk_scale(hs, rhs_of(y)));
-      Vec yn = y; trk_axpy(yn, Tab::B[0], z);
+      Vec z;
+      {
+        // y + q b: q A joins row R (resident: k3 is A in lane 0 and 0 elsewhere, so the FMA is uniform over the lanes)
+        Vec r = y;
+        if constexpr (RES) r.s[0] = __builtin_fma(qq, k3, y.s[0]); else r.R = __builtin_fma(qq, cA, y.R);
+        z = solve(r);
+        trk_axpy(z, -1.0, y);
+      }
+      Vec yn = y; trk_axpy(yn, Tab::B[0] / Tab::GAM, z);
       Vec u6;
       static_for<Tab::NS - 1>([&](auto kc) {
         constexpr int kk = 1 + decltype(kc)::value;
+        constexpr double bk = Tab::B[kk] / Tab::GAM, ek = Tab::E[kk] / Tab::GAM;
         z = solve(z);
-        trk_axpy(yn, Tab::B[kk], z);
-        if constexpr (kk == 1) u6 = trk_scale(Tab::E[1], z); else trk_axpy(u6, Tab::E[kk], z);
+        trk_axpy(yn, bk, z);
+        if constexpr (kk == 1) u6 = trk_scale(ek, z); else trk_axpy(u6, ek, z);
       });
 
-      // the candidate's site sum, formed directly (as the C restatement's right-hand side does) and independent of the error norm; an
-      // accepting lane takes it over with R and P, a rejecting lane keeps the sum of the state it keeps
-      double sg_new;
-      if constexpr (RES) sg_new = sites_only(yn.s); else sg_new = site_sum<G>(yn.s, lane);
       double err;
       if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
       // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
@@ -575,10 +585,9 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 #pragma unroll
         for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
         if constexpr (!RES) { y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; }
-        y.sg = acc ? sg_new : y.sg;
       } else {
         if (acc) {
-          static_cast<Vec&>(y) = yn; y.sg = sg_new;
+          y = yn;
           if constexpr (!CFG::LITERAL) tc += hs;
         }
       }
@@ -610,7 +619,6 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         if constexpr (!CFG::LITERAL) tc = te;
         te = tnx;
         asm volatile("" : "+v"(te));                      // pins this copy ahead of the row's stores: its wait then covers the load of tnx alone
-        // y.sg already is the direct sum of the rows emitted here
         emit(k, y, std::false_type{});
         ++k;
       }

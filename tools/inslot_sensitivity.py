@@ -32,8 +32,10 @@ def resident_fits(n, G, RPL):
     return G * RPL >= n + 2
 
 
-def lrp12_resident(th, n, G, RPL, y0, t, tables, rtol=1e-6, atol=1e-8, max_steps=100000, h0=0.0):
-    """One replica on G lanes x RPL rows, resident layout.  (sol [T, n + 2], status, accepted, rejected)"""
+def lrp12_resident(th, n, G, RPL, y0, t, tables, rtol=1e-6, atol=1e-8, max_steps=100000, h0=0.0, resolvent=False):
+    """One replica on G lanes x RPL rows, resident layout.  (sol [T, n + 2], status, accepted, rejected)
+    resolvent = True forms the first stage as the step loop of csrc/pk_dist_fast.hpp does: gamma z_1 =
+    solve(y + q b) - y with the weights B_k / gamma, E_k / gamma; False keeps the earlier solve(h f(y))."""
     assert resident_fits(n, G, RPL)
     GAM, LB, LE = tables
     NS = 12
@@ -51,6 +53,7 @@ def lrp12_resident(th, n, G, RPL, y0, t, tables, rtol=1e-6, atol=1e-8, max_steps
     k3c = np.zeros(G); k3c[0] = A
     y = np.where(live, np.asarray(y0, float)[np.where(live, slot, 0)], 0.0)
     m0, m1 = chain_split_resident(RPL)
+    WB, WE = (LB / GAM, LE / GAM) if resolvent else (LB, LE)
 
     def sites_only(v):
         w = v.copy(); w[0, 0] = 0.0; w[1, 0] = 0.0
@@ -112,13 +115,17 @@ def lrp12_resident(th, n, G, RPL, y0, t, tables, rtol=1e-6, atol=1e-8, max_steps
                 xP = float((r[:, 0] * ws0 + tt[:, 1:].sum(axis=1)).sum()) * qs
                 return cw * xP + tt
 
-            z = solve(hs * rhs(y, sg))
-            yn = y + LB[0] * z
+            if resolvent:
+                r = y.copy(); r[:, 0] = q * k3c + y[:, 0]
+                z = solve(r) - y
+            else:
+                z = solve(hs * rhs(y, sg))
+            yn = y + WB[0] * z
             e = np.zeros_like(y)
             for st in range(1, NS):
                 z = solve(z)
-                yn = yn + LB[st] * z
-                e = e + LE[st] * z
+                yn = yn + WB[st] * z
+                e = e + WE[st] * z
             bad, err = norm(e, y, yn)
             if bad or err > 1e300:
                 rej += 1; after_reject = True; h = 0.1 * hs

@@ -57,11 +57,14 @@ def pivot_inverses(piv, chained):
     return inv, worst
 
 
-def lrp12_lanes(th, n, G, RPL, y0, t, tables, chained, rtol=1e-6, atol=1e-8, max_steps=100000):
+def lrp12_lanes(th, n, G, RPL, y0, t, tables, chained, rtol=1e-6, atol=1e-8, max_steps=100000, h0=0.0, resolvent=False):
     """One replica on G lanes x RPL rows.  (sol [T, n + 2] as lane 0 and the site rows emit it, status, accepted, rejected,
-    worst chain error in units of its bound, largest relative spread of P over the lanes)"""
+    worst chain error in units of its bound, largest relative spread of P over the lanes)
+    resolvent = True forms the first stage as the step loop of csrc/pk_dist_fast.hpp does: gamma z_1 =
+    solve(y + q b) - y with the weights B_k / gamma, E_k / gamma; False keeps the earlier solve(h f(y))."""
     GAM, LB, LE = tables
     NS = 12
+    WB, WE = (LB / GAM, LE / GAM) if resolvent else (LB, LE)
     A, Bc, Cc, D = (float(v) for v in th[:4])
     site = np.arange(G)[:, None] + G * np.arange(RPL)[None, :]
     ok = site < n
@@ -99,6 +102,8 @@ def lrp12_lanes(th, n, G, RPL, y0, t, tables, chained, rtol=1e-6, atol=1e-8, max
     d1 = max(float(np.max(np.abs(fR) / (atol + rtol * np.abs(R)))), float(np.max(np.abs(fP) / (atol + rtol * np.abs(P)))),
              float(np.max(np.abs(fs) / (atol + rtol * np.abs(s)))))
     h = 0.01 * d0 / d1 if (d0 > 1e-5 and d1 > 1e-5) else 1e-6
+    if h0 > 0.0:
+        h = h0
     for k in range(1, nT):
         te = float(t[k])
         while True:
@@ -122,14 +127,18 @@ def lrp12_lanes(th, n, G, RPL, y0, t, tables, chained, rtol=1e-6, atol=1e-8, max
                 xP = (rP + q * (Cc * xR + float(tt.sum()))) * sinv
                 return xR, xP, cw * xP[:, None] + tt
 
-            fR, fP, fs = rhs(R, P, s)
-            zR, zP, zs = solve(hs * fR, hs * fP, hs * fs)
-            Rn, Pn, sn = R + LB[0] * zR, P + LB[0] * zP, s + LB[0] * zs
+            if resolvent:
+                zR, zP, zs = solve(q * A + R, P, s)
+                zR, zP, zs = zR - R, zP - P, zs - s
+            else:
+                fR, fP, fs = rhs(R, P, s)
+                zR, zP, zs = solve(hs * fR, hs * fP, hs * fs)
+            Rn, Pn, sn = R + WB[0] * zR, P + WB[0] * zP, s + WB[0] * zs
             eR, eP, es = np.zeros(G), np.zeros(G), np.zeros((G, RPL))
             for st in range(1, NS):
                 zR, zP, zs = solve(zR, zP, zs)
-                Rn, Pn, sn = Rn + LB[st] * zR, Pn + LB[st] * zP, sn + LB[st] * zs
-                eR, eP, es = eR + LE[st] * zR, eP + LE[st] * zP, es + LE[st] * zs
+                Rn, Pn, sn = Rn + WB[st] * zR, Pn + WB[st] * zP, sn + WB[st] * zs
+                eR, eP, es = eR + WE[st] * zR, eP + WE[st] * zP, es + WE[st] * zs
             bad, err = norm(eR, eP, es, R, P, s, Rn, Pn, sn)
             if bad or err > 1e300:
                 rej += 1; after_reject = True; h = 0.1 * hs
