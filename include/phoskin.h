@@ -364,6 +364,17 @@ double pk_time_solve_protein_batch(pk_ctx*, int iters, int model, int n_sites, i
                                    double* sol, double* flat, double* metric, int metric_id,
                                    int32_t* status, int32_t* n_steps);
 
+/* Wave pacing of the parked one-wave LRP12 distmod kernels.  The policy is the environment variable PK_DIST_SCHED, read
+ * once per process: off | lead | level | lead+level (pk_dist_sched_names); unset, the four-lane layouts (17 <= n_sites <= 32) run
+ * lead+level on grids of up to 4/3 of the device's resident waves and everything else runs off.  pk_dist_sched_parse returns the policy's bits (0 = off) or -1 for a value that is none of them; with such a value set, pk_solve_protein_batch fails with PK_ERR_ARG and names the valid ones.
+ * Results do not depend on the policy.  Pure host code, usable without a GPU. */
+int         pk_dist_sched_parse(const char* value);
+const char* pk_dist_sched_names(void);
+/* Wave timeline of the diagnostic kernel that PK_DIST_TRACE=1 selects for the n_sites = 27-30 trajectory + running-sum configuration
+ * (tools/dist_wave_timeline.py): `records` is a DEVICE buffer of `capacity` 32-byte records {u64 t_entry, t_exit (100 MHz); u32 block,
+ * hw_id, xcc_id, iterations}, one per workgroup, which every later traced launch of the process fills; NULL detaches it.  Synchronous. */
+int         pk_dist_trace_set(pk_ctx*, void* records, int64_t capacity);
+
 /* Machine peaks measured on the context's GPU, for bench.py's roofline fractions (the spec-sheet values are printed beside them):
  * sustained HBM copy rate in GB/s (read + written bytes; `bytes` >= 1 MiB per buffer, choose it well beyond the 256 MiB Infinity Cache)
  * and sustained FP64 vector FMA rate in TFLOP/s.  Both allocate and free their own buffers; < 0 on error. */

@@ -65,6 +65,7 @@ SYMBOLS = (
     "pk_protein_n_states", "pk_protein_n_params", "pk_protein_flat_len",
     "pk_solve_protein_batch", "pk_solve_protein_sens_batch", "pk_protein_sens_available", "pk_rhs_protein_batch", "pk_jacobian_protein_batch", "pk_steady_state_protein_batch", "pk_morris_build_batch", "pk_morris_effects_batch", "pk_score_fit_batch",
     "pk_solve_protein_batch_host", "pk_solve_protein_sens_batch_host", "pk_rhs_protein_batch_host", "pk_jacobian_protein_batch_host",
+    "pk_dist_sched_parse", "pk_dist_sched_names", "pk_dist_trace_set",
     "pk_time_solve_protein_batch", "pk_measure_hbm_gbs", "pk_measure_hbm_stream_gbs", "pk_measure_fp64_fma_tflops",
     "pk_network_create", "pk_network_destroy", "pk_network_n_states", "pk_network_n_var",
     "pk_network_rhs_batch", "pk_network_jacobian_batch", "pk_network_unpack_batch", "pk_network_simulate_batch",
@@ -160,6 +161,9 @@ def load():
     lib.pk_measure_hbm_gbs.restype = dbl; lib.pk_measure_hbm_gbs.argtypes = [vp, i64, i32]
     lib.pk_measure_hbm_stream_gbs.restype = dbl; lib.pk_measure_hbm_stream_gbs.argtypes = [vp, i64, i32, i32]
     lib.pk_measure_fp64_fma_tflops.restype = dbl; lib.pk_measure_fp64_fma_tflops.argtypes = [vp, i32]
+    lib.pk_dist_sched_parse.restype = i32; lib.pk_dist_sched_parse.argtypes = [C.c_char_p]
+    lib.pk_dist_sched_names.restype = C.c_char_p; lib.pk_dist_sched_names.argtypes = []
+    lib.pk_dist_trace_set.restype = i32; lib.pk_dist_trace_set.argtypes = [vp, vp, i64]
     lib.pk_time_solve_protein_batch.restype = dbl
     lib.pk_time_solve_protein_batch.argtypes = [vp, i32] + solve_args[1:]
     _lib = lib

@@ -317,9 +317,10 @@ int pk_solve_protein_batch(pk_ctx* c, int model, int n_sites, int64_t B, const d
                    (tpr_env == 1 || (tpr_env != 0 && B >= tpr_min));
   if (tpr)
     PK_HIP(c, pk::launch_tpr(a, model, c->stream));
-  else if (model == PK_MODEL_DIST && resolvent_method(o.method) && o.linsolve == PK_LINSOLVE_AUTO && !o.stage_form)
+  else if (model == PK_MODEL_DIST && resolvent_method(o.method) && o.linsolve == PK_LINSOLVE_AUTO && !o.stage_form) {
+    if (pk::dist_sched_env() < 0) return fail(c, PK_ERR_ARG, std::string("PK_DIST_SCHED must be one of: ") + pk::kDistSchedNames);
     pk::launch_dist_fast(a, o.method, c->stream);                      // throughput layout: 4-16 lanes per replica, shadowed or resident R / P rows
-  else if (rand_fast)
+  } else if (rand_fast)
     pk::launch_rand_fast(a, o.method, c->stream);                  // 2^n lanes per replica, shadowed mRNA row
   else
     kSolve[model][gidx(G)](a, o.method, structured, grid, c->stream);
@@ -554,6 +555,19 @@ int pk_jacobian_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B,
   rc = pk_jacobian_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<double>(o_J));
   if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
   return h.download();
+}
+
+int pk_dist_sched_parse(const char* value) { return pk::dist_sched_parse(value); }
+
+const char* pk_dist_sched_names(void) { return pk::kDistSchedNames; }
+
+int pk_dist_trace_set(pk_ctx* c, void* records, int64_t capacity) {
+  if (!c) return PK_ERR_ARG;
+  if (capacity < 0 || (records && capacity < 1)) return fail(c, PK_ERR_ARG, "capacity must be >= 1 with a buffer");
+  PK_HIP(c, hipSetDevice(c->device));
+  PK_HIP(c, hipStreamSynchronize(c->stream));                        // no traced launch of this context is still writing to the old buffer
+  PK_HIP(c, pk::dist_trace_set(records, (long long)capacity));
+  return PK_OK;
 }
 
 double pk_time_solve_protein_batch(pk_ctx* c, int iters, int model, int n_sites, int64_t B, const double* theta,

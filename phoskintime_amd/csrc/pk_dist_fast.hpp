@@ -130,6 +130,29 @@ template <int RPL, int NT> struct Parked<RPL, true, NT> {
 template <int RPL, bool PARK, int NT = 256, class CFG = DistAny, bool RES = false>
 constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<RPL, CFG::SLOT_MC, RES>() + RPL) * NT * sizeof(double) : 0; }
 
+// Wave pacing (SolveArgs::sched; the parked one-wave LRP12 kernels only, every other instantiation ignores the field).  The waves of a SIMD
+// share its VALU by priority, then by age, and nothing else in this kernel sets a priority: the policies below only tell the arbiter which
+// wave to prefer.  They move no work, wait on nothing and change no value; a wrong guess costs time, never progress.
+//   LEAD   when the grid exceeds the resident capacity R1 (SolveArgs::R1: more than one round of waves), one first-round wave per SIMD runs
+//          at priority 3 for its whole life, so that it ends early and the SIMD's next wave starts as early as possible.  Two rules name
+//          that wave: LEAD_SLOT, hardware wave slot 0 among the workgroups below R1; LEAD_BLOCK, the workgroups below R1 / 3;
+//   LEVEL  every other wave takes its priority from its own progress, the output index k of its slowest live replica: 2 before output
+//          PK_DSCHED_K2, 1 before PK_DSCHED_K1, 0 from there on (4 + 4 + 5 of the benchmark's 13 intervals), re-evaluated at the top of
+//          each step.  Two v_cmp on the lanes' k feed the scalar unit, which does the rest; with the policy off a uniform branch skips them.
+enum { PK_DSCHED_OFF = 0, PK_DSCHED_LEAD_SLOT = 1, PK_DSCHED_LEVEL = 2, PK_DSCHED_LEAD_BLOCK = 4 };
+constexpr int PK_DSCHED_K2 = 5, PK_DSCHED_K1 = 9;
+// s_getreg operands: id | offset << 6 | (size - 1) << 11.  HW_ID (register 4): wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]
+constexpr int PK_HWREG_HW_ID = 4 | (31 << 11), PK_HWREG_HW_ID_WAVE = 4 | (3 << 11), PK_HWREG_XCC_ID = 20 | (31 << 11);
+
+// Wave timeline of the diagnostic build (TRACE = 1, one instantiation in pk_inst_dist_fast12t.hip; no shipped kernel holds any of it):
+// lane 0 of each wave writes one record, at entry and again before finish(), to a buffer of its own that nothing else reads.
+struct DistTraceRec {
+  unsigned long long t_entry, t_exit;      // s_memrealtime (100 MHz)
+  unsigned block, hw_id, xcc_id, iters;    // blockIdx.x, raw HW_ID and XCC_ID, step-loop iterations of the wave
+};
+struct DistTraceBuf { DistTraceRec* rec; long long capacity; };
+template <int TRACE> struct DistTrace;     // get(): the buffer; specialised where the traced kernel is instantiated
+
 // NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
 //
 // RES = true is the RESIDENT layout, for sizes whose whole state fits the lane layout (G * RPL >= n + 2): the state vector is laid over
@@ -143,10 +166,47 @@ constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<
 //   * right-hand side (prologue only, for the initial step estimate): R and P are broadcast from their lanes; row 0 is
 //     fma(k1, P, fma(-dg0, X, k3)) with per-lane k1 = 0 | -Dsum | S_i, dg0 = B | -C | 1 + D_i, X = R | R | x_i, k3 = A | sg | 0;
 //   * the site sum skips the R and P slots; every reduction that steers a replica is still a group reduction.
-template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny, bool RES = false>
+template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 1), int NT = 256, class CFG = DistAny, bool RES = false, int TRACE = 0>
 __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) {
   using Tab = ResolventTab<METHOD>;
   using Vec = Stg<RPL, RES>;
+  constexpr bool PACE = PARK && NT == 64 && METHOD == PK_METHOD_LRP12;
+  static_assert(!TRACE || NT == 64, "the trace holds one record per workgroup: one wave each");
+  if constexpr (TRACE) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    const DistTraceBuf tb = DistTrace<TRACE>::get();
+    if (threadIdx.x == 0 && tb.rec && (long long)blockIdx.x < tb.capacity) {
+      DistTraceRec* r = tb.rec + blockIdx.x;
+      r->t_entry = t0; r->t_exit = 0; r->block = blockIdx.x; r->iters = 0;
+      r->hw_id = __builtin_amdgcn_s_getreg(PK_HWREG_HW_ID); r->xcc_id = __builtin_amdgcn_s_getreg(PK_HWREG_XCC_ID);
+    }
+  }
+  int witer = 0;                                            // TRACE only: this lane's trips through the step loop
+  auto trace_exit = [&]() {
+    if constexpr (TRACE) {
+      int it = witer;
+      for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(it, o); it = v > it ? v : it; }
+      const DistTraceBuf tb = DistTrace<TRACE>::get();
+      if (threadIdx.x == 0 && tb.rec && (long long)blockIdx.x < tb.capacity) {
+        DistTraceRec* r = tb.rec + blockIdx.x;
+        r->iters = (unsigned)it; r->t_exit = __builtin_amdgcn_s_memrealtime();
+      }
+    }
+  };
+  // wave pacing: everything here is uniform over the wave (kernel arguments, blockIdx, a hardware register) and runs on the scalar unit
+  bool paced = false;
+  if constexpr (PACE) {
+    const int sched = A.sched;
+    if (sched != PK_DSCHED_OFF) {
+      bool leader = false;
+      if ((int)gridDim.x > A.R1) {
+        if (sched & PK_DSCHED_LEAD_SLOT) leader = (int)blockIdx.x < A.R1 && __builtin_amdgcn_s_getreg(PK_HWREG_HW_ID_WAVE) == 0;
+        if (sched & PK_DSCHED_LEAD_BLOCK) leader = leader || (int)blockIdx.x < A.R1 / 3;
+      }
+      if (leader) __builtin_amdgcn_s_setprio(3);
+      paced = !leader && (sched & PK_DSCHED_LEVEL) != 0;
+    }
+  }
   extern __shared__ __align__(16) double park_lds[];
   Parked<RPL, PARK, NT> pk(park_lds);
   // the parked slots of every wave the launch bounds promise a CU (4 SIMDs x MINB) must fit its 160 KiB; the tightest entry of the launch
@@ -341,7 +401,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 
   emit(0, y, std::false_type{});
   int status = PK_ST_OK, nacc = 0;
-  if (T < 2) { finish(status, 0, 0); return; }
+  if (T < 2) { trace_exit(); finish(status, 0, 0); return; }
 
   const double rtol = A.rtol, atol = A.atol;
   // max-norm helpers over the whole system (sites of this lane + shadows, then across the group)
@@ -537,6 +597,13 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   while (true) {
     bool nonfin = false;
     while (true) {
+      if constexpr (TRACE) ++witer;
+      if constexpr (PACE) if (paced) {
+        // the slowest live replica of the wave decides: a replica that is done has left the loop and no longer votes
+        if (__builtin_amdgcn_ballot_w64(k < PK_DSCHED_K2) != 0) __builtin_amdgcn_s_setprio(2);
+        else if (__builtin_amdgcn_ballot_w64(k < PK_DSCHED_K1) != 0) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+      }
       const double tnx = A.t[k + 1 < T ? k + 1 : T - 1];   // the output time after te, fetched a whole step before a landing can need it
       // failure exits (step budget, vanishing step): status is set here and the NaN rows are written after the loop
       const bool over = (CFG::LITERAL ? nacc + nsec : nsec) >= A.max_steps;
@@ -634,6 +701,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   const int nrej = CFG::LITERAL ? nsec : nsec - nacc;
   if (status != PK_ST_OK)                               // a failed replica: NaN rows from the landing it failed at
     for (; k < T; ++k) emit(k, y, std::true_type{});
+  trace_exit();
   finish(status, nacc, nrej);
 }
 

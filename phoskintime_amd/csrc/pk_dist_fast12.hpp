@@ -6,13 +6,21 @@
 
 namespace pk {
 
+// PK_DIST_SCHED (read once per process): the wave-pacing policy of the parked one-wave kernels as PK_DSCHED_* bits (pk_dist_fast.hpp).
+// dist_sched_parse names the accepted values and returns -1 for anything else; the C entry points reject such a setting before a launch.
+// dist_sched_env: the parsed setting, PK_DSCHED_UNSET without one (the launch table's own choice applies).
+constexpr int PK_DSCHED_UNSET = 0x100;
+int dist_sched_parse(const char* v);
+int dist_sched_env();
+extern const char* const kDistSchedNames;
+
 // One instantiation: NT threads per workgroup, launch-uniform choices CFG, shadowed or resident rows (pk_dist_fast.hpp).
-template <int G, int RPL, bool PARK, int NT, class CFG, bool RES>
+template <int G, int RPL, bool PARK, int NT, class CFG, bool RES, int TRACE = 0>
 static void launch_cfg(const SolveArgs& a, hipStream_t st) {
   const long long rpb = NT / G;
   const long long nblk = (a.B + rpb - 1) / rpb;
   constexpr size_t lds = dist_fast_lds_bytes<RPL, PARK, NT, CFG, RES>();
-  auto kern = dist_fast_kernel<G, RPL, PK_METHOD_LRP12, PARK, (PARK ? 2 : 1), NT, CFG, RES>;
+  auto kern = dist_fast_kernel<G, RPL, PK_METHOD_LRP12, PARK, (PARK ? 2 : 1), NT, CFG, RES, TRACE>;
   if constexpr (lds > 48 * 1024) {
     static const bool once = [kern] {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -20,7 +28,29 @@ static void launch_cfg(const SolveArgs& a, hipStream_t st) {
     }();
     (void)once;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(NT), lds, st, a);
+  if constexpr (PARK && NT == 64) {
+    // the paced kernels: the policy, and the workgroups the device holds at once (occupancy of this kernel x compute units, asked once per
+    // kernel; a failed query reads as "everything fits one round", which keeps the leaders off)
+    static const int resident = [kern] {
+      int dev = 0, cus = 0, per_cu = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, NT, lds) != hipSuccess || per_cu < 1 || cus < 1) {
+        (void)hipGetLastError();
+        return 0x7fffffff;
+      }
+      return per_cu * cus;
+    }();
+    SolveArgs b = a;
+    // unset: what was measured.  Pacing pays while a SIMD gets at most one wave beyond its resident ones -- a grid of up
+    // to 4/3 of the resident capacity, the benchmark's 4 096 workgroups on 3 072 slots among them -- in the four-lane layouts; larger
+    // grids and the eight-lane layouts, which it slowed, run unpaced.  A setting of PK_DIST_SCHED applies to every grid (A/B runs)
+    const int env = dist_sched_env();
+    const bool pays = G == 4 && nblk <= (long long)resident + resident / 3;
+    b.sched = env == PK_DSCHED_UNSET ? (pays ? PK_DSCHED_LEAD_SLOT | PK_DSCHED_LEVEL : PK_DSCHED_OFF) : env < 0 ? (int)PK_DSCHED_OFF : env;
+    b.R1 = resident;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(NT), lds, st, b);
+  } else
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(NT), lds, st, a);
 }
 
 // The combinations the library's own callers produce get a kernel with those choices compiled in (no dead output paths, no bookkeeping
@@ -36,5 +66,8 @@ static void launch_nt(const SolveArgs& a, hipStream_t st) {
 
 // resident layout of the LRP12 table's (G, RPL) for n_sites = n, for the sizes with G * RPL >= n + 2 (pk_inst_dist_fast12r.hip)
 void launch_dist_fast12_resident(const SolveArgs& a, bool wg256, hipStream_t st);
+// the diagnostic build of the benchmark's kernel (4 x 8 resident, DistSolSum) with the wave timeline, and its buffer (pk_inst_dist_fast12t.hip)
+void launch_dist_fast12_traced(const SolveArgs& a, hipStream_t st);
+hipError_t dist_trace_set(void* records, long long capacity);
 
 }  // namespace pk

@@ -14,6 +14,36 @@
 
 namespace pk {
 
+const char* const kDistSchedNames = "off, lead, level, lead+level";
+
+// "lead" is the rule the measured timeline picked, hardware wave slot 0; lead:slot and lead:block name the two rules for A/B runs
+int dist_sched_parse(const char* v) {
+  if (!v || !*v) return -1;
+  if (!strcmp(v, "off")) return PK_DSCHED_OFF;
+  int bits = 0;
+  for (const char* p = v; *p;) {
+    const char* e = strchr(p, '+');
+    const size_t len = e ? (size_t)(e - p) : strlen(p);
+    auto is = [&](const char* w) { return strlen(w) == len && !strncmp(p, w, len); };
+    int b;
+    if (is("lead") || is("lead:slot")) b = PK_DSCHED_LEAD_SLOT;
+    else if (is("lead:block")) b = PK_DSCHED_LEAD_BLOCK;
+    else if (is("level")) b = PK_DSCHED_LEVEL;
+    else return -1;
+    if (bits & b) return -1;
+    bits |= b;
+    p += len;
+    if (e) { ++p; if (!*p) return -1; }
+  }
+  return bits;
+}
+
+// An unknown value reads as -1 here, and the C entry points refuse to launch (pk_capi.hip); a launch that gets here all the same runs unpaced
+int dist_sched_env() {
+  static const int v = [] { const char* e = getenv("PK_DIST_SCHED"); return e ? dist_sched_parse(e) : PK_DSCHED_UNSET; }();
+  return v;
+}
+
 template <int G, int RPL>
 static void launch_plain(const SolveArgs& a, hipStream_t st) { launch_nt<G, RPL, false, 256, false>(a, st); }
 

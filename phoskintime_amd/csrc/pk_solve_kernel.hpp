@@ -20,6 +20,9 @@ struct SolveArgs {
   double* sol; double* flat; double* metric; int32_t* status; int32_t* n_steps;
   long long B; int n_sites; int S; int P; int T; int F; int n_obs; int y0_batched; int metric_id;
   double rtol, atol, h0, rk4_h; int max_steps; int clip; int normalize; int stage_form;
+  // wave pacing of the parked one-wave LRP12 distmod kernels (pk_dist_fast.hpp, PK_DSCHED_*), filled by their launcher: the policy and the
+  // number of workgroups the device holds at once.  No other kernel reads them
+  int sched = 0; int R1 = 0;
 };
 
 // ------------------------------------------------------------------ RODAS4 (Hairer & Wanner, rodas.f METH=1)
