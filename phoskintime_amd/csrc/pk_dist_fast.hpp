@@ -24,38 +24,16 @@
 //     A stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
 //   * no LDS-pipe instruction in the solve chain; LDS only as thread-private parking space in the PARK layouts (below).
 //
+// pk_dist_rows.hpp holds the rows a lane carries (Stg) and what is done for every row of a lane -- the vector updates, both error norms,
+// the sign-bit OR and the clip -- once over the lane's row list, whichever layout the rows come from.  Wave pacing and the wave trace are
+// two helpers below (DistPace, DistWaveTrace), empty unless their flag is on.
+//
 // dR/dt = A - B R ; dP/dt = C R - (D + sum S_i) P + sum X_i ; dX_i/dt = S_i P - (1 + D_i) X_i
 #pragma once
-#include "pk_solve_kernel.hpp"
+#include "pk_dist_rows.hpp"
 
 namespace pk {
 
-template <int RPL, bool RES = false>
-struct Stg {               // one vector of the system as seen by a lane: a stage, a candidate, an error estimate
-  double s[RPL];           // this lane's site rows
-  double R, P;             // shadow rows (identical in every lane of the group)
-};
-template <int RPL>
-struct Stg<RPL, true> {    // resident layout: R and P are rows like any other (slot 0 and slot 1), nothing is shadowed
-  double s[RPL];           // this lane's slots: state lane + G * j
-};
-template <int RPL, bool RES>
-__device__ __forceinline__ void trk_axpy(Stg<RPL, RES>& acc, const double a, const Stg<RPL, RES>& u) {
-#pragma unroll
-  for (int j = 0; j < RPL; ++j) acc.s[j] = __builtin_fma(a, u.s[j], acc.s[j]);
-  if constexpr (!RES) {
-    acc.R = __builtin_fma(a, u.R, acc.R);
-    acc.P = __builtin_fma(a, u.P, acc.P);
-  }
-}
-template <int RPL, bool RES>
-__device__ __forceinline__ Stg<RPL, RES> trk_scale(const double a, const Stg<RPL, RES>& u) {
-  Stg<RPL, RES> r;
-#pragma unroll
-  for (int j = 0; j < RPL; ++j) r.s[j] = a * u.s[j];
-  if constexpr (!RES) { r.R = a * u.R; r.P = a * u.P; }
-  return r;
-}
 // the sum over all sites of a replica: a tree over the lane's rows, then the group reduction
 template <int G, int RPL>
 __device__ __forceinline__ double site_sum(const double (&s)[RPL], int lane) { return gsum<G>(tree_sum(s), lane); }
@@ -144,6 +122,35 @@ constexpr int PK_DSCHED_K2 = 5, PK_DSCHED_K1 = 9;
 // s_getreg operands: id | offset << 6 | (size - 1) << 11.  HW_ID (register 4): wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]
 constexpr int PK_HWREG_HW_ID = 4 | (31 << 11), PK_HWREG_HW_ID_WAVE = 4 | (3 << 11), PK_HWREG_XCC_ID = 20 | (31 << 11);
 
+template <bool PACE> struct DistPace {           // PACE = false: nothing
+  __device__ __forceinline__ void enter(const SolveArgs&) {}
+  __device__ __forceinline__ void step(int) const {}
+};
+template <> struct DistPace<true> {
+  bool paced = false;
+  // everything here is uniform over the wave (kernel arguments, blockIdx, a hardware register) and runs on the scalar unit
+  __device__ __forceinline__ void enter(const SolveArgs& A) {
+    const int sched = A.sched;
+    if (sched != PK_DSCHED_OFF) {
+      bool leader = false;
+      if ((int)gridDim.x > A.R1) {
+        if (sched & PK_DSCHED_LEAD_SLOT) leader = (int)blockIdx.x < A.R1 && __builtin_amdgcn_s_getreg(PK_HWREG_HW_ID_WAVE) == 0;
+        if (sched & PK_DSCHED_LEAD_BLOCK) leader = leader || (int)blockIdx.x < A.R1 / 3;
+      }
+      if (leader) __builtin_amdgcn_s_setprio(3);
+      paced = !leader && (sched & PK_DSCHED_LEVEL) != 0;
+    }
+  }
+  // k: this lane's output index.  The slowest live replica of the wave decides: a replica that is done has left the loop and no longer votes
+  __device__ __forceinline__ void step(const int k) const {
+    if (paced) {
+      if (__builtin_amdgcn_ballot_w64(k < PK_DSCHED_K2) != 0) __builtin_amdgcn_s_setprio(2);
+      else if (__builtin_amdgcn_ballot_w64(k < PK_DSCHED_K1) != 0) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+    }
+  }
+};
+
 // Wave timeline of the diagnostic build (TRACE = 1, one instantiation in pk_inst_dist_fast12t.hip; no shipped kernel holds any of it):
 // lane 0 of each wave writes one record, at entry and again before finish(), to a buffer of its own that nothing else reads.
 struct DistTraceRec {
@@ -152,6 +159,34 @@ struct DistTraceRec {
 };
 struct DistTraceBuf { DistTraceRec* rec; long long capacity; };
 template <int TRACE> struct DistTrace;     // get(): the buffer; specialised where the traced kernel is instantiated
+
+template <int TRACE> struct DistWaveTrace {
+  int witer = 0;                           // this lane's trips through the step loop
+  __device__ __forceinline__ void enter() {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    const DistTraceBuf tb = DistTrace<TRACE>::get();
+    if (threadIdx.x == 0 && tb.rec && (long long)blockIdx.x < tb.capacity) {
+      DistTraceRec* r = tb.rec + blockIdx.x;
+      r->t_entry = t0; r->t_exit = 0; r->block = blockIdx.x; r->iters = 0;
+      r->hw_id = __builtin_amdgcn_s_getreg(PK_HWREG_HW_ID); r->xcc_id = __builtin_amdgcn_s_getreg(PK_HWREG_XCC_ID);
+    }
+  }
+  __device__ __forceinline__ void step() { ++witer; }
+  __device__ __forceinline__ void exit() const {
+    int it = witer;
+    for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(it, o); it = v > it ? v : it; }
+    const DistTraceBuf tb = DistTrace<TRACE>::get();
+    if (threadIdx.x == 0 && tb.rec && (long long)blockIdx.x < tb.capacity) {
+      DistTraceRec* r = tb.rec + blockIdx.x;
+      r->iters = (unsigned)it; r->t_exit = __builtin_amdgcn_s_memrealtime();
+    }
+  }
+};
+template <> struct DistWaveTrace<0> {      // the shipped kernels: nothing
+  __device__ __forceinline__ void enter() {}
+  __device__ __forceinline__ void step() {}
+  __device__ __forceinline__ void exit() const {}
+};
 
 // NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
 //
@@ -170,43 +205,11 @@ template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 
 __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) {
   using Tab = ResolventTab<METHOD>;
   using Vec = Stg<RPL, RES>;
-  constexpr bool PACE = PARK && NT == 64 && METHOD == PK_METHOD_LRP12;
   static_assert(!TRACE || NT == 64, "the trace holds one record per workgroup: one wave each");
-  if constexpr (TRACE) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    const DistTraceBuf tb = DistTrace<TRACE>::get();
-    if (threadIdx.x == 0 && tb.rec && (long long)blockIdx.x < tb.capacity) {
-      DistTraceRec* r = tb.rec + blockIdx.x;
-      r->t_entry = t0; r->t_exit = 0; r->block = blockIdx.x; r->iters = 0;
-      r->hw_id = __builtin_amdgcn_s_getreg(PK_HWREG_HW_ID); r->xcc_id = __builtin_amdgcn_s_getreg(PK_HWREG_XCC_ID);
-    }
-  }
-  int witer = 0;                                            // TRACE only: this lane's trips through the step loop
-  auto trace_exit = [&]() {
-    if constexpr (TRACE) {
-      int it = witer;
-      for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(it, o); it = v > it ? v : it; }
-      const DistTraceBuf tb = DistTrace<TRACE>::get();
-      if (threadIdx.x == 0 && tb.rec && (long long)blockIdx.x < tb.capacity) {
-        DistTraceRec* r = tb.rec + blockIdx.x;
-        r->iters = (unsigned)it; r->t_exit = __builtin_amdgcn_s_memrealtime();
-      }
-    }
-  };
-  // wave pacing: everything here is uniform over the wave (kernel arguments, blockIdx, a hardware register) and runs on the scalar unit
-  bool paced = false;
-  if constexpr (PACE) {
-    const int sched = A.sched;
-    if (sched != PK_DSCHED_OFF) {
-      bool leader = false;
-      if ((int)gridDim.x > A.R1) {
-        if (sched & PK_DSCHED_LEAD_SLOT) leader = (int)blockIdx.x < A.R1 && __builtin_amdgcn_s_getreg(PK_HWREG_HW_ID_WAVE) == 0;
-        if (sched & PK_DSCHED_LEAD_BLOCK) leader = leader || (int)blockIdx.x < A.R1 / 3;
-      }
-      if (leader) __builtin_amdgcn_s_setprio(3);
-      paced = !leader && (sched & PK_DSCHED_LEVEL) != 0;
-    }
-  }
+  DistWaveTrace<TRACE> trace;
+  trace.enter();
+  DistPace<PARK && NT == 64 && METHOD == PK_METHOD_LRP12> pace;
+  pace.enter(A);
   extern __shared__ __align__(16) double park_lds[];
   Parked<RPL, PARK, NT> pk(park_lds);
   // the parked slots of every wave the launch bounds promise a CU (4 SIMDs x MINB) must fit its 160 KiB; the tightest entry of the launch
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   });
   const double Dsum = th[3] + gsum<G>(lsum, lane);
   // the sum over the site slots of a resident lane: row 0 of lanes 0 and 1 (R and P) stays out
-  auto sites_only = [&](const double (&s)[RPL]) {
+  auto sites_only = [&](const auto& s) {
     double v[RPL];
 #pragma unroll
     for (int j = 0; j < RPL; ++j) v[j] = s[j];
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // ---- state
   const double* y0p = A.y0 + (A.y0_batched ? rep * S : 0);
   Vec y;
-  if constexpr (!RES) { y.R = y0p[0]; y.P = y0p[1]; }
+  if constexpr (!RES) { y.R() = y0p[0]; y.P() = y0p[1]; }
 #pragma unroll
   for (int j = 0; j < RPL; ++j) {
     const int i = l + G * j;
@@ -282,14 +285,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     // values (two idle-row zeros of either sign included: a -0 only sends the wave down the literal path) and run the literal clip only
     // when some lane of the wave has a sign bit set -- a branch on the scalar unit, uniform over the wave.  Same bits on both paths.
     bool clip_now = CFG::clip(A);
-    if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
-      typedef int dwords __attribute__((ext_vector_type(2)));      // element 1 = the high dword; as a shift of the 64 bits the OR is done on both dwords
-      int sgn = 0;
-      if constexpr (!RES) sgn = __builtin_bit_cast(dwords, v.R).y | __builtin_bit_cast(dwords, v.P).y;
-#pragma unroll
-      for (int j = 0; j < RPL; ++j) sgn |= __builtin_bit_cast(dwords, v.s[j]).y;
-      clip_now = __builtin_amdgcn_ballot_w64(sgn < 0) != 0;
-    }
+    if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) clip_now = __builtin_amdgcn_ballot_w64(sign_or(v) < 0) != 0;
     auto val = [&](double x, int state) {
       if (nan_fill) return __builtin_nan("");
       double r = (CFG::LITERAL && CFG::clip(A)) ? ((x < 0.0) ? 0.0 : x) : x;          // the run-time kernel clips value by value
@@ -298,15 +294,12 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     };
     Vec c = v;                                          // the clipped state
     if constexpr (!CFG::LITERAL && !nan_fill) if (clip_now) {
-      // keeps this a branch: without it the compiler folds the test into each select
-      if constexpr (RES) asm volatile("" : "+v"(c.s[0])); else asm volatile("" : "+v"(c.R));
-      if constexpr (!RES) { c.R = (c.R < 0.0) ? 0.0 : c.R; c.P = (c.P < 0.0) ? 0.0 : c.P; }
-#pragma unroll
-      for (int j = 0; j < RPL; ++j) c.s[j] = (c.s[j] < 0.0) ? 0.0 : c.s[j];
+      asm volatile("" : "+v"(c.s[Vec::tree_row(0)]));   // keeps this a branch: without it the compiler folds the test into each select
+      clip_rows(c);
     }
     double vR = 0.0, vP = 0.0;
     if constexpr (!RES) {
-      vR = val(c.R, 0); vP = val(c.P, 1);
+      vR = val(c.R(), 0); vP = val(c.P(), 1);
       if (l == 0) {
         if (CFG::sol(A)) { srow[-2] = vR; srow[-1] = vP; }
         if (CFG::flat(A)) { if (k >= 5) fl[k - 5] = vR; fl[T5 + k] = vP; }
@@ -401,36 +394,10 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
 
   emit(0, y, std::false_type{});
   int status = PK_ST_OK, nacc = 0;
-  if (T < 2) { trace_exit(); finish(status, 0, 0); return; }
+  if (T < 2) { trace.exit(); finish(status, 0, 0); return; }
 
   const double rtol = A.rtol, atol = A.atol;
-  // max-norm helpers over the whole system (sites of this lane + shadows, then across the group)
-  auto q = [&](double e, double ya, double yb) { return fabs(e) * approx_rcp(__builtin_fma(rtol, fmax(fabs(ya), fabs(yb)), atol)); };
-  auto group_max = [&](const Vec& num, const Vec& a, const Vec& b) {   // NaN-propagating: the initial step estimate; DistAny
-    auto mx = [](double p, double r) { return (p > r || p != p) ? p : r; };
-    double m;
-    if constexpr (RES) m = q(num.s[0], a.s[0], b.s[0]); else m = mx(q(num.R, a.R, b.R), q(num.P, a.P, b.P));
-#pragma unroll
-    for (int j = (RES ? 1 : 0); j < RPL; ++j) m = mx(m, q(num.s[j], a.s[j], b.s[j]));
-    return gmax<G>(m, lane);
-  };
-  // The error norm of the step loop: the ratios of group_max for the error estimate e against the accepted state y and the candidate yn,
-  // their maximum with v_max_f64 (one instruction per element and per DPP level; it DROPS a NaN).  A NaN ratio (a NaN in a row's error or
-  // scale, inf * 0, 0 * inf) is found by unordered compares on pairs of ratios and turned into +inf, which v_max_f64 carries through the
-  // group; an inf ratio is the maximum anyway.  The loop treats +inf and NaN alike (reject, then the PK_ST_NONFINITE test), and for finite
-  // ratios the maximum has the bits group_max returns.
-  auto err_norm = [&](const Vec& e, const Vec& y, const Vec& yn) {
-    constexpr int X = RES ? 0 : 2;                     // resident: the lane's RPL slots are all there is
-    double r[RPL + X];
-    if constexpr (!RES) { r[0] = q(e.R, y.R, yn.R); r[1] = q(e.P, y.P, yn.P); }
-    static_for<RPL>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      r[X + j] = q(e.s[j], y.s[j], yn.s[j]);
-    });
-    double m = tree_max(r);
-    if (any_nan(r)) m = __builtin_inf();
-    return gmax_num<G>(m, lane);
-  };
+  const DistNorm<G, RPL, RES> norm{rtol, atol, lane};
   auto rhs_of = [&](const Vec& Y, const double sg) {       // f(Y) with sg the site sum of Y: the prologue's initial step estimate only
     Vec f;
     if constexpr (RES) {
@@ -443,11 +410,11 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         else f.s[j] = __builtin_fma(sr, Pb, -dg * Y.s[j]);
       });
     } else {
-      f.R = __builtin_fma(-cB, Y.R, cA);
-      f.P = __builtin_fma(cC, Y.R, __builtin_fma(-Dsum, Y.P, sg));
+      f.R() = __builtin_fma(-cB, Y.R(), cA);
+      f.P() = __builtin_fma(cC, Y.R(), __builtin_fma(-Dsum, Y.P(), sg));
       static_for<RPL>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        f.s[j] = __builtin_fma(pk.template get<K_SR + j>(), Y.P, -pk.template get<K_DG + j>() * Y.s[j]);
+        f.s[j] = __builtin_fma(pk.template get<K_SR + j>(), Y.P(), -pk.template get<K_DG + j>() * Y.s[j]);
       });
     }
     return f;
@@ -459,9 +426,15 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   double h;
   {
     double sg0;
-    if constexpr (RES) sg0 = sites_only(y.s); else sg0 = site_sum<G>(y.s, lane);
+    if constexpr (RES) sg0 = sites_only(y.s);
+    else {
+      double v[RPL];                                      // the site rows alone: y.s ends with the shadow rows
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) v[j] = y.s[j];
+      sg0 = site_sum<G>(v, lane);
+    }
     const Vec f0 = rhs_of(y, sg0);
-    const double d0 = group_max(y, y, y), d1 = group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
+    const double d0 = norm.group_max(y, y, y), d1 = norm.group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;
@@ -526,7 +499,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   auto solve = [&](const Vec& r) {
     Vec u;
     double xR = 0.0;
-    if constexpr (!RES) xR = r.R * winvR;
+    if constexpr (!RES) xR = r.R() * winvR;
     double t[RPL];
 #pragma unroll
     for (int j = 0; j < RPL; ++j) t[j] = r.s[j] * winv[j];
@@ -545,10 +518,10 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
     } else {
       const double St = gsum<G>(tree_sum(t), lane);
-      const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), r.P) * sinv;
+      const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), r.P()) * sinv;
 #pragma unroll
       for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
-      u.R = xR; u.P = xP;
+      u.R() = xR; u.P() = xP;
     }
     return u;
   };
@@ -571,7 +544,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     }
     bool b;
     if constexpr (RES) b = ((isR || isP) && nonfinite(rows[0])) || nonfinite(sites_only(rows));
-    else b = (nonfinite(y.R)) || (nonfinite(y.P)) || (nonfinite(site_sum<G>(rows, lane)));
+    else b = (nonfinite(y.R())) || (nonfinite(y.P())) || (nonfinite(site_sum<G>(rows, lane)));
     return gmax<G>(b ? 1.0 : 0.0, lane);
   };
   // A, B, C of the same test.  Resident: they are not kept in registers through the loop (B and C live in the diagonal slots of lanes 0
@@ -597,13 +570,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   while (true) {
     bool nonfin = false;
     while (true) {
-      if constexpr (TRACE) ++witer;
-      if constexpr (PACE) if (paced) {
-        // the slowest live replica of the wave decides: a replica that is done has left the loop and no longer votes
-        if (__builtin_amdgcn_ballot_w64(k < PK_DSCHED_K2) != 0) __builtin_amdgcn_s_setprio(2);
-        else if (__builtin_amdgcn_ballot_w64(k < PK_DSCHED_K1) != 0) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      }
+      trace.step();
+      pace.step(k);
       const double tnx = A.t[k + 1 < T ? k + 1 : T - 1];   // the output time after te, fetched a whole step before a landing can need it
       // failure exits (step budget, vanishing step): status is set here and the NaN rows are written after the loop
       const bool over = (CFG::LITERAL ? nacc + nsec : nsec) >= A.max_steps;
@@ -622,7 +590,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       {
         // y + q b: q A joins row R (resident: k3 is A in lane 0 and 0 elsewhere, so the FMA is uniform over the lanes)
         Vec r = y;
-        if constexpr (RES) r.s[0] = __builtin_fma(qq, k3, y.s[0]); else r.R = __builtin_fma(qq, cA, y.R);
+        if constexpr (RES) r.s[0] = __builtin_fma(qq, k3, y.s[0]); else r.R() = __builtin_fma(qq, cA, y.R());
         z = solve(r);
         trk_axpy(z, -1.0, y);
       }
@@ -637,7 +605,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       });
 
       double err;
-      if constexpr (CFG::LITERAL) err = group_max(u6, y, yn); else err = err_norm(u6, y, yn);
+      if constexpr (CFG::LITERAL) err = norm.group_max(u6, y, yn); else err = norm.err_norm(u6, y, yn);
       // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
       // a rejection too (acc = false), so the state is settled before the non-finite exit below looks at it
       const bool acc = (err <= 1.0);
@@ -651,7 +619,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         }
 #pragma unroll
         for (int j = 0; j < RPL; ++j) y.s[j] = yn.s[j];
-        if constexpr (!RES) { y.R = acc ? yn.R : y.R; y.P = acc ? yn.P : y.P; }
+        #pragma unroll
+        for (int x = 0; x < Vec::X; ++x) y.s[RPL + x] = acc ? yn.s[RPL + x] : y.s[RPL + x];
       } else {
         if (acc) {
           y = yn;
@@ -701,7 +670,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   const int nrej = CFG::LITERAL ? nsec : nsec - nacc;
   if (status != PK_ST_OK)                               // a failed replica: NaN rows from the landing it failed at
     for (; k < T; ++k) emit(k, y, std::true_type{});
-  trace_exit();
+  trace.exit();
   finish(status, nacc, nrej);
 }
 

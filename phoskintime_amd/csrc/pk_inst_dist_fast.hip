@@ -1,5 +1,5 @@
 // Instantiations + launcher of the distributive-model throughput kernel (pk_dist_fast.hpp): RODAS4 and LRP8.
-// LRP12 (the default method) has its own, finer layout table in pk_inst_dist_fast12.hip.
+// LRP12 (the default method) has its own, finer layout table: launch_table12 in pk_dist_fast12.hpp, entered through launch_dist_fast12.
 #include "pk_dist_fast.hpp"
 #include "pk_launch.hpp"
 

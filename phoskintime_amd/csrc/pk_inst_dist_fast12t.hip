@@ -1,6 +1,6 @@
 // The traced build of the benchmark's distmod kernel (pk_dist_fast.hpp, TRACE = 1: 4 x 8 resident, parked, one wave per workgroup,
 // DistSolSum) in a translation unit of its own, with the device global that carries its record buffer.  Selected by PK_DIST_TRACE=1
-// (pk_inst_dist_fast12r.hip); tools/dist_wave_timeline.py reads the records.
+// (launch_dist_fast12, pk_inst_dist_fast12.hip); tools/dist_wave_timeline.py reads the records.
 #include "pk_dist_fast12.hpp"
 
 namespace pk {
