@@ -435,9 +435,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     }
     const Vec f0 = rhs_of(y, sg0);
     const double d0 = norm.group_max(y, y, y), d1 = norm.group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
 
   // Arrow factors of M = I - q J (q = gamma h) for the current step size.

@@ -18,6 +18,7 @@
 // forced landing point) and uses the bucket of its START time throughout, so each step sees an autonomous system.
 #pragma once
 #include "pk_network.hpp"
+#include "pk_step.hpp"
 #include "../../include/phoskin.h"
 
 namespace pk {
@@ -408,6 +409,7 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
       d0 = fmax(d0, fabs(y[k]) / sc); d1 = fmax(d1, fabs(net_state_rhs(n, L, k)) / sc);
     }
     d0 = block_max(d0, red); d1 = block_max(d1, red);
+    // step_h0 of pk_step.hpp, written out: the call changes register allocation and spill counts in these kernels
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;
@@ -461,8 +463,7 @@ __device__ __forceinline__ void net_rosw_solve(const NetDev& n, const NetSolveAr
         if (block_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; break; }
         continue;
       }
-      double fac = cbrt(err) * (1.0 / 0.9);
-      fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+      const double fac = step_fac(cbrt(err));
       double hnew = hs / fac;
       if (err <= 1.0) {
         ++nacc;

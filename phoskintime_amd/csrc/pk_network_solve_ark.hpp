@@ -236,6 +236,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark_kernel(const NetDev n, c
 #pragma unroll
     for (int k = 0; k < NR; ++k) if (own && k < 2 + ns) { d0 = fmax(d0, q(y[k], y[k])); d1 = fmax(d1, q(f[k], y[k])); }
     d0 = block_max(d0, red); d1 = block_max(d1, red);
+    // step_h0 of pk_step.hpp, written out: the call changes register allocation and spill counts in these kernels
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;
@@ -326,8 +327,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark_kernel(const NetDev n, c
         if (block_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; break; }
         continue;
       }
-      double fac = sqrt(sqrt(err)) * safety_inv;                             // embedded order 3: err^(1/4)
-      fac = fmax(grow_inv, fmin(5.0, fac));
+      const double fac = step_fac(sqrt(sqrt(err)), grow_inv, safety_inv);  // embedded order 3: err^(1/4)
       double hnew = hs * net_rcp(fac);
       if (err <= 1.0) {
         ++nacc;
@@ -601,6 +601,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark2_kernel(const NetDev n, 
 #pragma unroll
     for (int k = 0; k < NR; ++k) if (own && k < 1 + nst) { d0 = fmax(d0, q(y[k], y[k])); d1 = fmax(d1, q(f[k], y[k])); }
     d0 = block_max(d0, red); d1 = block_max(d1, red);
+    // step_h0 of pk_step.hpp, written out: the call changes register allocation and spill counts in these kernels
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;
@@ -675,8 +676,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark2_kernel(const NetDev n, 
         if (block_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; break; }
         continue;
       }
-      double fac = sqrt(sqrt(err)) * safety_inv;
-      fac = fmax(grow_inv, fmin(5.0, fac));
+      const double fac = step_fac(sqrt(sqrt(err)), grow_inv, safety_inv);
       double hnew = hs * net_rcp(fac);
       if (err <= 1.0) {
         ++nacc;

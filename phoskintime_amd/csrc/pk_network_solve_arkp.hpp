@@ -347,6 +347,7 @@ __device__ __forceinline__ void net_solve_arkp_body(const NetDev& n, const NetSo
 #pragma unroll
     for (int k = 0; k < NRL; ++k) if (valid[k]) { d0 = fmax(d0, q(y[k], y[k])); d1 = fmax(d1, q(f[k], y[k])); }
     d0 = block_max(d0, red); d1 = block_max(d1, red);
+    // step_h0 of pk_step.hpp, written out: the call changes register allocation and spill counts in these kernels
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;

@@ -178,6 +178,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_reg_kernel(const NetDev n, c
 #pragma unroll
     for (int j = 0; j < MAXS; ++j) if (j < ns) { d0 = fmax(d0, q(ys[j], ys[j])); d1 = fmax(d1, q(fs[j], ys[j])); }
     d0 = block_max(d0, red); d1 = block_max(d1, red);
+    // step_h0 of pk_step.hpp, written out: the call changes register allocation and spill counts in these kernels
     h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
     if (A.h0 > 0.0) h = A.h0;
     if (!(h > 0.0) || h != h) h = 1e-6;
@@ -249,8 +250,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_reg_kernel(const NetDev n, c
         if (block_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; break; }
         continue;
       }
-      double fac = cbrt(err) * (1.0 / 0.9);
-      fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+      const double fac = step_fac(cbrt(err));
       double hnew = hs * net_rcp(fac);
       if (err <= 1.0) {
         ++nacc;

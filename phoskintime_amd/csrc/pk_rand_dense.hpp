@@ -158,9 +158,7 @@ __global__ __launch_bounds__(rand_dense_threads<NB>()) void rand_dense_kernel(co
   {
     rhs_into(y, zs, 1.0);
     const double d0 = err_norm(y, y, y), d1 = err_norm(zs, y, y);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
   auto fail_from = [&](int kk) { for (; kk < T; ++kk) out.emit(kk, y, true); };
   bool after_reject = false;
@@ -191,8 +189,7 @@ __global__ __launch_bounds__(rand_dense_threads<NB>()) void rand_dense_kernel(co
       if (wg_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs / fac;
     if (err <= 1.0) {
       ++nacc;

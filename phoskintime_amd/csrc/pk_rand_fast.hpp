@@ -139,9 +139,7 @@ __global__ __launch_bounds__(256) void rand_fast_kernel(const SolveArgs A) {
     const double f0 = rhs_row(y, yR), fR = __builtin_fma(-cB, yR, cA);
     const double d0 = gmax<G>(mxn(ratio(y, y, y), ratio(yR, yR, yR)), lane);
     const double d1 = gmax<G>(mxn(ratio(f0, y, y), ratio(fR, yR, yR)), lane);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
 
   // M = I - q J on the 2^n coupled rows, inverted in registers (Gauss-Jordan, no pivoting: M is an M-matrix)
@@ -211,8 +209,7 @@ __global__ __launch_bounds__(256) void rand_fast_kernel(const SolveArgs A) {
       if (bad != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs * fast_rcp(fac);
     if (err <= 1.0) {
       ++nacc;

@@ -181,9 +181,7 @@ __global__ __launch_bounds__(256, 2) void rand_fastr_kernel(const SolveArgs A) {
     const double fR = __builtin_fma(-cB, yR, cA);
     const double d0 = norm(y, yR, y, yR, y, yR);
     const double d1 = norm(f0, fR, y, yR, y, yR);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
 
   // M = I - q J (NM x NM), rows l + G * s per lane, inverted in registers (Gauss-Jordan, no pivoting: M-matrix)
@@ -278,8 +276,7 @@ __global__ __launch_bounds__(256, 2) void rand_fastr_kernel(const SolveArgs A) {
       if (gmax<G>(nf ? 1.0 : 0.0, lane) != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs * fast_rcp(fac);
     if (err <= 1.0) {
       ++nacc;

@@ -260,9 +260,7 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA)
       m0 = mx(m0, fabs(Y[row * KC]) / sc); m1 = mx(m1, fabs(ZS[row * KC]) / sc);
     }
     const double d0 = wg_max(m0, red), d1 = wg_max(m1, red);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
   const double* const kB = Tab::B;
   const double* const kE = Tab::E;
@@ -327,8 +325,7 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA)
       if (wg_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs / fac;
     if (err <= 1.0) {
       ++nacc;

@@ -610,9 +610,7 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const S
     double f0[NR];
     sys.apply_base(y_at, [&](auto ic, double v) { f0[decltype(ic)::value] = v; }, cA);
     const double d0 = norm(y_at, y_at, y_at), d1 = norm([&](auto ic) { return f0[decltype(ic)::value]; }, y_at, y_at);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
     h = bcast<GP, 0>(h);                                      // the base lane's estimate, for the whole group
   }
 
@@ -683,8 +681,7 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const S
       if (nf) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs * fast_rcp(fac);
     if (err <= 1.0) {
       ++nacc;

@@ -121,9 +121,7 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
     const double f0 = rhs<MODEL, G>(c, y[0], n, S, row, lane);
     const double sc = __builtin_fma(rtol, fabs(y[0]), atol);
     const double d0 = gmax<G>(fabs(y[0]) / sc, lane), d1 = gmax<G>(fabs(f0) / sc, lane);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
   const double* const kB = Tab::B;                         // indexed by the (uniform) stage counter of the rolled loop
   const double* const kE = Tab::E;
@@ -178,8 +176,7 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
       if (bad != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs * fast_rcp(fac);
     if (err <= 1.0) {
       ++nacc;

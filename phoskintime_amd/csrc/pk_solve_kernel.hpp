@@ -12,6 +12,7 @@
 #include <cstdint>
 #include "../../include/phoskin.h"
 #include "pk_linsolve.hpp"
+#include "pk_step.hpp"
 
 namespace pk {
 
@@ -215,9 +216,7 @@ __global__ __launch_bounds__(256) void solve_kernel(const SolveArgs A) {
       const double f0 = f_of(y);
       const double sc = __builtin_fma(rtol, fabs(y), atol);
       const double d0 = gmax<G>(fabs(y) / sc, lane), d1 = gmax<G>(fabs(f0) / sc, lane);
-      h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-      if (A.h0 > 0.0) h = A.h0;
-      if (!(h > 0.0) || h != h) h = 1e-6;
+      h = step_h0(d0, d1, A.h0);
     }
 
     if constexpr (METHOD == PK_METHOD_RODAS4 || METHOD == PK_METHOD_LRP8 || METHOD == PK_METHOD_LRP12) {
@@ -265,8 +264,7 @@ __global__ __launch_bounds__(256) void solve_kernel(const SolveArgs A) {
           if (gmax<G>((nonfinite(y)) ? 1.0 : 0.0, lane) != 0.0) { status |= PK_ST_NONFINITE; out.fill_nan(k); break; }
           continue;
         }
-        double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-        fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+        const double fac = step_fac(root_q(err, Tab::Q));
         double hnew = hs / fac;
         if (err <= 1.0) {
           ++nacc;
@@ -342,8 +340,7 @@ __global__ __launch_bounds__(256) void solve_kernel(const SolveArgs A) {
           if (gmax<G>((nonfinite(y)) ? 1.0 : 0.0, lane) != 0.0) { status |= PK_ST_NONFINITE; out.fill_nan(k); break; }
           continue;
         }
-        double fac = ((hist < 2) ? sqrt(err) : cbrt(err)) * (1.0 / 0.9);
-        fac = fmax(0.5, fmin(5.0, fac));                                // growth <= 2x per step
+        const double fac = step_fac((hist < 2) ? sqrt(err) : cbrt(err), 0.5);  // growth <= 2x per step
         const double hnew = hs / fac;
         if (err <= 1.0) {
           ++nacc;

@@ -209,9 +209,7 @@ __global__ __launch_bounds__(256) void tpr_kernel(const SolveArgs A) {
     double f0[NR];
     rhs_of(y, f0);
     const double d0 = norm(y, y, y), d1 = norm(f0, y, y);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
 
   // ---- factors of M = I - q J and the solve, all in this lane
@@ -298,8 +296,7 @@ __global__ __launch_bounds__(256) void tpr_kernel(const SolveArgs A) {
       if (nf) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs * fast_rcp(fac);
     if (err <= 1.0) {
       ++nacc;

@@ -260,9 +260,7 @@ __global__ __launch_bounds__(256) void wide_chain_kernel(const SolveArgs A) {
   {
     rhs_into(y, z, 1.0);
     const double d0 = err_norm(y, y, y), d1 = err_norm(z, y, y);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
   auto fail_from = [&](int kk) { for (; kk < T; ++kk) out.emit(kk, y, true); };
   bool after_reject = false;
@@ -291,8 +289,7 @@ __global__ __launch_bounds__(256) void wide_chain_kernel(const SolveArgs A) {
       if (wg_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(root_q(err, Tab::Q));
     double hnew = hs / fac;
     if (err <= 1.0) {
       ++nacc;
@@ -518,9 +515,7 @@ __global__ __launch_bounds__(256) void wide_rand_kernel(const SolveArgs A, doubl
   {
     rhs_into(y, f, 0, nullptr);
     const double d0 = norm_of(y, y, y), d1 = norm_of(f, y, y);
-    h = (d0 > 1e-5 && d1 > 1e-5) ? 0.01 * d0 / d1 : 1e-6;
-    if (A.h0 > 0.0) h = A.h0;
-    if (!(h > 0.0) || h != h) h = 1e-6;
+    h = step_h0(d0, d1, A.h0);
   }
   auto fail_from = [&](int kk) { for (; kk < T; ++kk) out.emit(kk, y, true); };
   bool after_reject = false;
@@ -603,8 +598,7 @@ __global__ __launch_bounds__(256) void wide_rand_kernel(const SolveArgs A, doubl
         if (wg_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
         continue;
       }
-      double fac = sqrt(sqrt(err)) * (1.0 / 0.9);
-      fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+      const double fac = step_fac(sqrt(sqrt(err)));
       double hnew = hs / fac;
       if (err <= 1.0) {
         ++nacc;
@@ -678,8 +672,7 @@ __global__ __launch_bounds__(256) void wide_rand_kernel(const SolveArgs A, doubl
       if (wg_max(bad, red) != 0.0) { status |= PK_ST_NONFINITE; fail_from(k); break; }
       continue;
     }
-    double fac = cbrt(err) * (1.0 / 0.9);
-    fac = fmax(1.0 / 6.0, fmin(5.0, fac));
+    const double fac = step_fac(cbrt(err));
     double hnew = hs / fac;
     if (err <= 1.0) {
       ++nacc;
