@@ -1,5 +1,6 @@
 // pk_capi.hip -- the C ABI of libphoskin_hip.so (include/phoskin.h): argument checking, launch geometry,
-// context / stream management and the host-pointer convenience variants.  No kernels here (pk_solve_kernel.hpp).
+// context / stream management and the host-pointer convenience variants.  No kernels here (pk_solve_kernel.hpp); which kernel the
+// per-protein solve launches is decided in pk_plan.hpp.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -9,6 +10,7 @@
 #include <string>
 #include "../../include/phoskin.h"
 #include "pk_launch.hpp"
+#include "pk_plan.hpp"
 #include "pk_sens.hpp"
 
 // A growable device buffer that outlives calls: the `_host` entry points stage through one, kernels that need per-replica HBM scratch
@@ -70,20 +72,78 @@ size_t aligned(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 // larger ones are copied array by array straight from / to the caller's (pageable) memory
 constexpr size_t kPackedLimit = 4u << 20;
 
-bool resolvent_method(int m) { return m == PK_METHOD_RODAS4 || m == PK_METHOD_LRP8 || m == PK_METHOD_LRP12; }
-int group_width(int S) { return S <= 8 ? 8 : S <= 16 ? 16 : S <= 32 ? 32 : S <= 64 ? 64 : 0; }
+using pk::group_width;
+
+// model and n_sites name a system: the range test of the size queries (check_model says which part failed)
+bool protein_in_range(int model, int n_sites, bool cap_rand = true) {
+  return model >= 0 && model <= 2 && n_sites >= 1 && !(cap_rand && model == PK_MODEL_RAND && n_sites > 20);
+}
 
 int check_model(pk_ctx* c, int model, int n_sites) {
   if (model < 0 || model > 2) return fail(c, PK_ERR_ARG, "model must be 0 (dist), 1 (succ) or 2 (rand)");
   if (n_sites < 1) return fail(c, PK_ERR_ARG, "n_sites must be >= 1");
   if (model == PK_MODEL_RAND && n_sites > 20) return fail(c, PK_ERR_UNSUPPORTED, "randmod: n_sites <= 20 (2^n states, 2^n + n + 3 parameters per replica)");
   if (model != PK_MODEL_RAND && pk::n_states(model, n_sites) > 64 && !pk::wide_chain_fits(pk::n_states(model, n_sites), n_sites))
-    return fail(c, PK_ERR_UNSUPPORTED, "distmod / succmod: n_sites <= 1276 (sixteen LDS vectors of n_sites + 2 doubles per workgroup)");
+    return fail(c, PK_ERR_UNSUPPORTED, pk::kChainTooWide);
   return PK_OK;
 }
-// systems beyond one wavefront's lane groups (pk_wide.hpp): distmod / succmod with more than 64 states, randmod with n_sites >= 7
-bool is_wide(int model, int n_sites) { return model == PK_MODEL_RAND ? n_sites >= 7 : pk::n_states(model, n_sites) > 64; }
 
+// The environment switches of the per-protein selection (pk_plan.hpp), read once per process.
+const pk::ProteinSwitches& protein_switches() {
+  static const pk::ProteinSwitches once = [] {
+    pk::ProteinSwitches s;
+    const auto read = [](const char* name, int& value) { if (const char* v = getenv(name)) value = atoi(v); };
+    // PK_WIDE_RAND_EXACT picks among the exact kernels and the approximate one at randmod n = 7 / 8 -- the tests hold them to agreement:
+    //   1 (default)  parity elimination: the odd-popcount block of M is diagonal, the even Schur complement (64 x 64 at n = 7, 128 x 128
+    //                at n = 8) is inverted in registers (pk_rand_parity.hpp)
+    //   2            n = 7: the full 128 x 128 inverse in registers (pk_rand_dense.hpp, round 2's kernel); n = 8: block elimination over
+    //                the popcount levels with the Schur complements in LDS (pk_rand_level.hpp)
+    //   0            the n-cube kernel (approximate factorisation), which stays the path for n >= 9
+    read("PK_WIDE_RAND_EXACT", s.wide_rand_exact);
+    // A/B switch of the tests: PK_RAND_LEVEL6=1 runs randmod n = 6 on the level-block kernel instead of the one-wave kernel
+    read("PK_RAND_LEVEL6", s.rand_level6);
+    // [r3] randmod n = 6 with the default method: parity elimination in ONE wave per replica (pk_rand_parity.hpp, 8 x 8 lanes over the 32 x 32
+    // even Schur complement): 2.1-2.2 M replicas/s against 0.59 M of the 64 x 64 in-register inverse of pk_rand_fast.hpp (same box, B = 16 384 ... 65 536).
+    // PK_RAND_PARITY56: 0 = the old kernel, 1 = also n = 5 (dev; 4 x 4 lanes per replica, four replicas per wave: 9.1-10.2 M against 8.2-9.4 M of the 32-lane kernel at B >= 16 384,
+    // but 0.63 against 0.44 ms per launch at B = 7 -- not worth a second default; one wave per replica: 5.2-5.8 M)
+    read("PK_RAND_PARITY56", s.rand_parity56);
+    // PK_TPR=0 / 1 pins the lane-group / the thread-per-replica family for dev A/B runs, as opts->kernel does for callers
+    read("PK_TPR", s.tpr);
+    s.dist_sched = pk::dist_sched_env();
+    return s;
+  }();
+  return once;
+}
+
+// Copy or default the options; a max_steps that is not positive means the default.
+pk_solver_opts solver_opts(const pk_solver_opts* in) {
+  pk_solver_opts o;
+  if (in) o = *in; else pk_default_opts(&o);
+  if (o.max_steps <= 0) o.max_steps = 100000;
+  return o;
+}
+
+pk::SolveArgs solve_args(int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched, const double* t, int T,
+                         const pk_solver_opts& o, double* sol, double* flat, double* metric, int metric_id, int32_t* status, int32_t* n_steps) {
+  pk::SolveArgs a;
+  a.theta = theta; a.y0 = y0; a.t = t; a.sol = sol; a.flat = flat; a.metric = metric; a.status = status; a.n_steps = n_steps;
+  a.B = B; a.n_sites = n_sites; a.S = pk::n_states(model, n_sites); a.P = pk::n_params(model, n_sites); a.T = T;
+  a.F = pk_protein_flat_len(model, n_sites, T); a.n_obs = n_sites; a.y0_batched = y0_is_batched ? 1 : 0; a.metric_id = metric_id;
+  a.rtol = o.rtol; a.atol = o.atol; a.h0 = o.h0; a.rk4_h = o.rk4_h; a.max_steps = o.max_steps; a.clip = o.clip_nonneg; a.normalize = o.normalize; a.stage_form = o.stage_form;
+  return a;
+}
+
+// pk_ctx_scratch_launch's view of the n-cube kernel whose vectors do not fit LDS
+hipError_t wide_rand_scratch_launch(void* scratch, hipStream_t stream, void* args) {
+  return pk::launch_wide_rand(*static_cast<const pk::SolveArgs*>(args), static_cast<double*>(scratch), stream);
+}
+
+// workgroups of an RHS / Jacobian launch: 256 / G replicas each on the lane-group kernels, 256 rows each beyond 64 states
+long long row_blocks(int S, long long B) {
+  if (S > 64) return (B * S + 255) / 256;
+  const long long rpb = 256 / group_width(S);
+  return (B + rpb - 1) / rpb;
+}
 
 int gidx(int G) { return G == 8 ? 0 : G == 16 ? 1 : G == 32 ? 2 : 3; }
 #define PK_ROW(base, M) {pk::base##M##_g8, pk::base##M##_g16, pk::base##M##_g32, pk::base##M##_g64}
@@ -115,16 +175,10 @@ void pk_default_opts(pk_solver_opts* o) {
   o->err_norm = PK_NORM_DEFAULT;
 }
 
-int pk_protein_n_states(int model, int n_sites) {
-  if (model < 0 || model > 2 || n_sites < 1 || (model == PK_MODEL_RAND && n_sites > 20)) return PK_ERR_ARG;
-  return pk::n_states(model, n_sites);
-}
-int pk_protein_n_params(int model, int n_sites) {
-  if (model < 0 || model > 2 || n_sites < 1 || (model == PK_MODEL_RAND && n_sites > 20)) return PK_ERR_ARG;
-  return pk::n_params(model, n_sites);
-}
+int pk_protein_n_states(int model, int n_sites) { return protein_in_range(model, n_sites) ? pk::n_states(model, n_sites) : PK_ERR_ARG; }
+int pk_protein_n_params(int model, int n_sites) { return protein_in_range(model, n_sites) ? pk::n_params(model, n_sites) : PK_ERR_ARG; }
 int pk_protein_flat_len(int model, int n_sites, int T) {
-  if (model < 0 || model > 2 || n_sites < 1 || T < 1) return PK_ERR_ARG;
+  if (!protein_in_range(model, n_sites, false) || T < 1) return PK_ERR_ARG;
   return (T > 5 ? T - 5 : 0) + T + n_sites * T;
 }
 
@@ -169,7 +223,7 @@ int pk_ctx_device(pk_ctx* c) { return c->device; }
 void* pk_ctx_stream(pk_ctx* c) { return (void*)c->stream; }
 int pk_ctx_fail(pk_ctx* c, int code, const char* msg) { return fail(c, code, msg ? msg : ""); }
 // the scratch arena for the workspace kernels of pk_network.hip: reserve `bytes` and launch under the lock, ordered after the previous
-// scratch user whatever stream that one ran on (the pattern of the wide randmod kernels in pk_solve_protein_batch)
+// scratch user whatever stream that one ran on (the n-cube randmod kernel of pk_solve_protein_batch goes the same way)
 int pk_ctx_scratch_launch(pk_ctx* c, size_t bytes, hipError_t (*launch)(void* scratch, hipStream_t stream, void* user), void* user) {
   std::lock_guard<std::recursive_mutex> g(c->mu);
   int rc = arena_reserve(c, c->scratch, bytes);
@@ -217,113 +271,35 @@ int pk_solve_protein_batch(pk_ctx* c, int model, int n_sites, int64_t B, const d
   if (B == 0) return PK_OK;
   if (!theta || !y0 || !t) return fail(c, PK_ERR_ARG, "theta, y0 and t must be non-null");
   if (metric && (metric_id < 0 || metric_id > 4)) return fail(c, PK_ERR_ARG, "unknown metric_id");
-  pk_solver_opts o;
-  if (opts_in) o = *opts_in; else pk_default_opts(&o);
+  const pk_solver_opts o = solver_opts(opts_in);
   if (o.method < 0 || o.method > 5 || o.method == PK_METHOD_DP5) return fail(c, PK_ERR_ARG, "unknown method (PK_METHOD_DP5 is a network integrator)");
   if (o.method != PK_METHOD_RK4 && !(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
   if (o.method == PK_METHOD_RK4 && !(o.rk4_h > 0.0)) return fail(c, PK_ERR_ARG, "rk4_h must be > 0");
-  if (o.max_steps <= 0) o.max_steps = 100000;
+  const pk::SolveArgs a = solve_args(model, n_sites, B, theta, y0, y0_is_batched, t, T, o, sol, flat, metric, metric_id, status, n_steps);
 
-  pk::SolveArgs a;
-  a.theta = theta; a.y0 = y0; a.t = t; a.sol = sol; a.flat = flat; a.metric = metric; a.status = status; a.n_steps = n_steps;
-  a.B = B; a.n_sites = n_sites; a.S = pk::n_states(model, n_sites); a.P = pk::n_params(model, n_sites); a.T = T;
-  a.F = pk_protein_flat_len(model, n_sites, T); a.n_obs = n_sites; a.y0_batched = y0_is_batched ? 1 : 0; a.metric_id = metric_id;
-  a.rtol = o.rtol; a.atol = o.atol; a.h0 = o.h0; a.rk4_h = o.rk4_h; a.max_steps = o.max_steps; a.clip = o.clip_nonneg; a.normalize = o.normalize; a.stage_form = o.stage_form;
-
-  if (o.kernel < PK_KERNEL_AUTO || o.kernel > PK_KERNEL_TPR) return fail(c, PK_ERR_ARG, "unknown opts->kernel");
-  if (is_wide(model, n_sites)) {
-    // one workgroup per replica (pk_wide.hpp).  distmod / succmod: LRP12 with exact structured solves; randmod: ROS34PW2-W on the n-cube
-    // (selected by any of the implicit one-step methods: there is no exact sparse resolvent for the LRP / RODAS family at this size)
-    if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
-    PK_HIP(c, hipSetDevice(c->device));
-    if (model == PK_MODEL_RAND) {
-      if (!resolvent_method(o.method) || o.stage_form)
-        return fail(c, PK_ERR_UNSUPPORTED, "randmod n_sites >= 7: method must be LRP12 / LRP8 / RODAS4 in resolvent form (n = 7: LRP12 with the dense inverse; beyond: additive Runge-Kutta on the n-cube)");
-      // PK_WIDE_RAND_EXACT (read once) picks among the exact kernels and the approximate one -- the tests hold them to agreement:
-      //   1 (default)  parity elimination: the odd-popcount block of M is diagonal, the even Schur complement (64 x 64 at n = 7, 128 x 128
-      //                at n = 8) is inverted in registers (pk_rand_parity.hpp)
-      //   2            n = 7: the full 128 x 128 inverse in registers (pk_rand_dense.hpp, round 2's kernel); n = 8: block elimination over
-      //                the popcount levels with the Schur complements in LDS (pk_rand_level.hpp)
-      //   0            the n-cube kernel below (approximate factorisation), which stays the path for n >= 9
-      static const int exact_env = [] { const char* v = getenv("PK_WIDE_RAND_EXACT"); return v ? atoi(v) : 1; }();
-      if (n_sites == 7 && exact_env == 1 && pk::rand_dense_available(7)) { PK_HIP(c, pk::launch_rand_parity(a, c->stream, o.kernel != PK_KERNEL_AUTO)); return PK_OK; }
-      if (pk::rand_dense_available(n_sites) && exact_env != 0) {   // n = 7, PK_WIDE_RAND_EXACT=2 (PK_WIDE_RAND_DENSE=0 also selects the n-cube kernel)
-        PK_HIP(c, pk::launch_rand_dense(a, c->stream));
-        return PK_OK;
-      }
-      if (n_sites == 8 && exact_env != 0) {
-        PK_HIP(c, exact_env == 2 ? pk::launch_rand_level(a, c->stream) : pk::launch_rand_parity(a, c->stream, o.kernel != PK_KERNEL_AUTO));
-        return PK_OK;
-      }
-      double* scr = nullptr;
-      if (!pk::wide_rand_in_lds(n_sites)) {
-        // the scratch rows are shared by every launch of this context: reserve + launch under the lock, and order the launch after the
-        // previous scratch user whatever stream that one ran on
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        rc = arena_reserve(c, c->scratch, pk::wide_rand_scratch_bytes(n_sites, B));
-        if (rc) return rc;
-        scr = (double*)c->scratch.p;
-        if (c->scratch_used) PK_HIP(c, hipStreamWaitEvent(c->stream, c->scratch_ev, 0));
-        PK_HIP(c, pk::launch_wide_rand(a, scr, c->stream));
-        PK_HIP(c, hipEventRecord(c->scratch_ev, c->stream));
-        c->scratch_used = true;
-      } else
-        PK_HIP(c, pk::launch_wide_rand(a, scr, c->stream));
-    } else {
-      if (o.method != PK_METHOD_LRP12 || o.stage_form)
-        return fail(c, PK_ERR_UNSUPPORTED, "distmod / succmod with more than 64 states integrate with method LRP12 (the default) only");
-      PK_HIP(c, pk::launch_wide_chain(a, model, c->stream));
-    }
-    PK_HIP(c, hipGetLastError());
-    return PK_OK;
-  }
-  // A/B switch of the tests: PK_RAND_LEVEL6=1 (read once) runs randmod n = 6 on the level-block kernel instead of the one-wave kernel
-  static const int level6_env = [] { const char* v = getenv("PK_RAND_LEVEL6"); return v ? atoi(v) : 0; }();
-  if (model == PK_MODEL_RAND && n_sites == 6 && level6_env == 1 && o.method == PK_METHOD_LRP12 && !o.stage_form) {
-    if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
-    PK_HIP(c, hipSetDevice(c->device));
-    PK_HIP(c, pk::launch_rand_level(a, c->stream));
-    return PK_OK;
-  }
-  // [r3] randmod n = 6 with the default method: parity elimination in ONE wave per replica (pk_rand_parity.hpp, 8 x 8 lanes over the 32 x 32
-  // even Schur complement): 2.1-2.2 M replicas/s against 0.59 M of the 64 x 64 in-register inverse below (same box, B = 16 384 ... 65 536).
-  // PK_RAND_PARITY56 (read once): 0 = the old kernel, 1 = also n = 5 (dev; 4 x 4 lanes per replica, four replicas per wave: 9.1-10.2 M against 8.2-9.4 M of the 32-lane kernel at B >= 16 384,
-  // but 0.63 against 0.44 ms per launch at B = 7 -- not worth a second default; one wave per replica: 5.2-5.8 M)
-  static const int parity56_env = [] { const char* v = getenv("PK_RAND_PARITY56"); return v ? atoi(v) : -1; }();
-  if (model == PK_MODEL_RAND && ((n_sites == 6 && parity56_env != 0) || (n_sites == 5 && parity56_env == 1)) && o.method == PK_METHOD_LRP12 &&
-      o.linsolve == PK_LINSOLVE_AUTO && !o.stage_form) {
-    if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
-    PK_HIP(c, hipSetDevice(c->device));
-    PK_HIP(c, pk::launch_rand_parity(a, c->stream));
-    return PK_OK;
-  }
-  const bool rand_fast = model == PK_MODEL_RAND && resolvent_method(o.method) && (o.linsolve == PK_LINSOLVE_AUTO || a.S > 64) && !o.stage_form;
-  if (a.S > 64 && !rand_fast)       // n = 6: the in-register inverse of pk_rand_fast.hpp is the only solver (every `linsolve` value selects it)
-    return fail(c, PK_ERR_UNSUPPORTED, "randmod n_sites = 6 (S = 65): only method RODAS4 / LRP8 in resolvent form (the generic kernels hold one state per lane)");
-  const int G = a.S > 64 ? 64 : group_width(a.S);
-  const long long rpb = 256 / G;
-  const long long nblk = (B + rpb - 1) / rpb;
-  if (nblk > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
-  const bool structured = (o.linsolve != PK_LINSOLVE_DENSE) && (model != PK_MODEL_RAND);
+  pk::ProteinFacts facts;
+  facts.tpr_available = pk::tpr_available(model, n_sites);
+  facts.rand_dense_available = pk::rand_dense_available(n_sites);
+  facts.wide_chain_fits = pk::wide_chain_fits(a.S, n_sites);
+  const pk::ProteinPlan plan = pk::protein_plan(model, n_sites, B, o, protein_switches(), facts);
+  if (plan.code != PK_OK)         // the launch limit of the chosen path is one of the plan's answers; the PK_DIST_SCHED refusal ends in the names the parser accepts
+    return fail(c, plan.code, plan.kernel == pk::ProteinKernel::DistFast ? std::string(plan.refusal) + pk::kDistSchedNames : plan.refusal);
   PK_HIP(c, hipSetDevice(c->device));
-  dim3 grid((unsigned)nblk);
-  // small systems, large batches: one lane per replica (64 replicas per wave: the batch must be large enough to occupy the SIMDs).
-  // Thresholds from tools/gpu_bench_dev.py tprB (crossover against the lane-group kernels).  opts->kernel pins the family (sharded runs
-  // that must reproduce single-GPU bits); the PK_TPR=0 / 1 environment variable (read once per process) does the same for dev A/B runs.
-  static const int tpr_env_once = [] { const char* v = getenv("PK_TPR"); return v ? atoi(v) : -1; }();
-  const int tpr_env = o.kernel == PK_KERNEL_GROUP ? 0 : o.kernel == PK_KERNEL_TPR ? 1 : tpr_env_once;
-  const long long tpr_min = (model == PK_MODEL_SUCC) ? (n_sites <= 8 ? 16384 : 32768) : (model == PK_MODEL_RAND) ? 32768 : (n_sites <= 8 ? 32768 : 49152);
-  const bool tpr = o.method == PK_METHOD_LRP12 && o.linsolve == PK_LINSOLVE_AUTO && !o.stage_form && pk::tpr_available(model, n_sites) &&
-                   (tpr_env == 1 || (tpr_env != 0 && B >= tpr_min));
-  if (tpr)
-    PK_HIP(c, pk::launch_tpr(a, model, c->stream));
-  else if (model == PK_MODEL_DIST && resolvent_method(o.method) && o.linsolve == PK_LINSOLVE_AUTO && !o.stage_form) {
-    if (pk::dist_sched_env() < 0) return fail(c, PK_ERR_ARG, std::string("PK_DIST_SCHED must be one of: ") + pk::kDistSchedNames);
-    pk::launch_dist_fast(a, o.method, c->stream);                      // throughput layout: 4-16 lanes per replica, shadowed or resident R / P rows
-  } else if (rand_fast)
-    pk::launch_rand_fast(a, o.method, c->stream);                  // 2^n lanes per replica, shadowed mRNA row
-  else
-    kSolve[model][gidx(G)](a, o.method, structured, grid, c->stream);
+  using K = pk::ProteinKernel;
+  switch (plan.kernel) {
+    case K::Group: kSolve[model][gidx(plan.G)](a, o.method, plan.structured, dim3((unsigned)plan.launches), c->stream); break;
+    case K::Tpr: PK_HIP(c, pk::launch_tpr(a, model, c->stream)); break;
+    case K::DistFast: pk::launch_dist_fast(a, o.method, c->stream); break;
+    case K::RandFast: pk::launch_rand_fast(a, o.method, c->stream); break;
+    case K::RandParity: PK_HIP(c, pk::launch_rand_parity(a, c->stream, plan.pinned_family)); break;
+    case K::RandLevel: PK_HIP(c, pk::launch_rand_level(a, c->stream)); break;
+    case K::RandDense: PK_HIP(c, pk::launch_rand_dense(a, c->stream)); break;
+    case K::WideChain: PK_HIP(c, pk::launch_wide_chain(a, model, c->stream)); break;
+    case K::WideRand:               // the scratch rows, where the vectors do not fit LDS, are shared by every launch of this context
+      if (pk::wide_rand_in_lds(n_sites)) PK_HIP(c, pk::launch_wide_rand(a, nullptr, c->stream));
+      else if ((rc = pk_ctx_scratch_launch(c, pk::wide_rand_scratch_bytes(n_sites, B), wide_rand_scratch_launch, const_cast<pk::SolveArgs*>(&a)))) return rc;
+      break;
+  }
   PK_HIP(c, hipGetLastError());
   return PK_OK;
 }
@@ -335,14 +311,14 @@ int pk_rhs_protein_batch(pk_ctx* c, int model, int n_sites, int64_t B, const dou
   if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
   if (B == 0) return PK_OK;
   if (!theta || !y || !dydt) return fail(c, PK_ERR_ARG, "null pointer");
-  const int S = pk::n_states(model, n_sites), P = pk::n_params(model, n_sites), G = S > 64 ? 1 : group_width(S);
-  const long long rpb = 256 / G, nblk = (S > 64 ? (B * S + 255) / 256 : (B + rpb - 1) / rpb);
+  const int S = pk::n_states(model, n_sites), P = pk::n_params(model, n_sites);
+  const long long nblk = row_blocks(S, B);
   if (nblk > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
   PK_HIP(c, hipSetDevice(c->device));
   dim3 grid((unsigned)nblk);
   if (S > 64 && model != PK_MODEL_RAND) pk::launch_chain_rhs_wide(model, theta, y, dydt, (long long)B, n_sites, S, P, c->stream);
   else if (S > 64) pk::launch_rand_rhs_wide(theta, y, dydt, (long long)B, n_sites, S, P, c->stream);
-  else kRhs[model][gidx(G)](theta, y, dydt, (long long)B, n_sites, S, P, grid, c->stream);
+  else kRhs[model][gidx(group_width(S))](theta, y, dydt, (long long)B, n_sites, S, P, grid, c->stream);
   PK_HIP(c, hipGetLastError());
   return PK_OK;
 }
@@ -354,14 +330,14 @@ int pk_jacobian_protein_batch(pk_ctx* c, int model, int n_sites, int64_t B, cons
   if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
   if (B == 0) return PK_OK;
   if (!theta || !J) return fail(c, PK_ERR_ARG, "null pointer");
-  const int S = pk::n_states(model, n_sites), P = pk::n_params(model, n_sites), G = S > 64 ? 1 : group_width(S);
-  const long long rpb = 256 / G, nblk = (S > 64 ? (B * S + 255) / 256 : (B + rpb - 1) / rpb);
+  const int S = pk::n_states(model, n_sites), P = pk::n_params(model, n_sites);
+  const long long nblk = row_blocks(S, B);
   if (nblk > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
   PK_HIP(c, hipSetDevice(c->device));
   dim3 grid((unsigned)nblk);
   if (S > 64 && model != PK_MODEL_RAND) pk::launch_chain_jac_wide(model, theta, J, (long long)B, n_sites, S, P, c->stream);
   else if (S > 64) pk::launch_rand_jac_wide(theta, J, (long long)B, n_sites, S, P, c->stream);
-  else kJac[model][gidx(G)](theta, J, (long long)B, n_sites, S, P, grid, c->stream);
+  else kJac[model][gidx(group_width(S))](theta, J, (long long)B, n_sites, S, P, grid, c->stream);
   PK_HIP(c, hipGetLastError());
   return PK_OK;
 }
@@ -432,13 +408,20 @@ struct HostCall {
     }
     return PK_OK;
   }
+  // the tail of every `_host` entry point: stage the inputs, make the device-pointer call, fetch the outputs (after a refusal, only
+  // wait for the copies already queued)
+  template <class Inner> int run(Inner inner) {
+    int rc = upload();
+    if (rc) return rc;
+    if ((rc = inner())) { (void)hipStreamSynchronize(c->stream); return rc; }
+    return download();
+  }
 };
 }  // namespace
 extern "C" {
 
 int pk_protein_sens_available(int model, int n_sites) {
-  if (model < 0 || model > 2 || n_sites < 1) return 0;
-  return pk::sens_available(model, n_sites) ? 1 : 0;
+  return protein_in_range(model, n_sites, false) && pk::sens_available(model, n_sites) ? 1 : 0;
 }
 
 int pk_solve_protein_sens_batch(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched,
@@ -453,17 +436,11 @@ int pk_solve_protein_sens_batch(pk_ctx* c, int model, int n_sites, int64_t B, co
     return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)");
   if (B == 0) return PK_OK;
   if (!theta || !y0 || !t || !flat || !dflat) return fail(c, PK_ERR_ARG, "theta, y0, t, flat and dflat must be non-null");
-  pk_solver_opts o;
-  if (opts_in) o = *opts_in; else pk_default_opts(&o);
+  const pk_solver_opts o = solver_opts(opts_in);
   if (o.method != PK_METHOD_LRP12 || o.stage_form) return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities integrate with method LRP12 (the default) only");
   if (!(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
-  if (o.max_steps <= 0) o.max_steps = 100000;
-  pk::SensArgs sa;
-  pk::SolveArgs& a = sa.s;
-  a.theta = theta; a.y0 = y0; a.t = t; a.sol = nullptr; a.flat = flat; a.metric = nullptr; a.status = status; a.n_steps = n_steps;
-  a.B = B; a.n_sites = n_sites; a.S = pk::n_states(model, n_sites); a.P = pk::n_params(model, n_sites); a.T = T;
-  a.F = pk_protein_flat_len(model, n_sites, T); a.n_obs = n_sites; a.y0_batched = y0_is_batched ? 1 : 0; a.metric_id = 0;
-  a.rtol = o.rtol; a.atol = o.atol; a.h0 = o.h0; a.rk4_h = o.rk4_h; a.max_steps = o.max_steps; a.clip = o.clip_nonneg; a.normalize = o.normalize; a.stage_form = 0;
+  pk::SensArgs sa;              // no trajectory and no metric: the observables and their derivatives (stage_form is 0 here)
+  sa.s = solve_args(model, n_sites, B, theta, y0, y0_is_batched, t, T, o, nullptr, flat, nullptr, 0, status, n_steps);
   sa.dflat = dflat;
   if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
   PK_HIP(c, hipSetDevice(c->device));
@@ -488,11 +465,10 @@ int pk_solve_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B, co
   const size_t o_th = h.add_in(theta, (size_t)B * P * 8), o_y0 = h.add_in(y0, ny0 * 8), o_t = h.add_in(t, (size_t)T * 8);
   const size_t o_sol = h.add_out(sol, (size_t)B * T * S * 8), o_flat = h.add_out(flat, (size_t)B * F * 8), o_met = h.add_out(metric, (size_t)B * 8),
                o_st = h.add_out(status, (size_t)B * 4), o_ns = h.add_out(n_steps, (size_t)B * 8);
-  if ((rc = h.upload())) return rc;
-  rc = pk_solve_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<const double>(o_y0), y0_is_batched, h.dev<const double>(o_t), T, opts,
-                              h.dev<double>(o_sol), h.dev<double>(o_flat), h.dev<double>(o_met), metric_id, h.dev<int32_t>(o_st), h.dev<int32_t>(o_ns));
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  return h.download();
+  return h.run([&] {
+    return pk_solve_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<const double>(o_y0), y0_is_batched, h.dev<const double>(o_t), T, opts,
+                                  h.dev<double>(o_sol), h.dev<double>(o_flat), h.dev<double>(o_met), metric_id, h.dev<int32_t>(o_st), h.dev<int32_t>(o_ns));
+  });
 }
 
 int pk_solve_protein_sens_batch_host(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched,
@@ -514,11 +490,10 @@ int pk_solve_protein_sens_batch_host(pk_ctx* c, int model, int n_sites, int64_t 
   const size_t o_th = h.add_in(theta, (size_t)B * P * 8), o_y0 = h.add_in(y0, ny0 * 8), o_t = h.add_in(t, (size_t)T * 8);
   const size_t o_flat = h.add_out(flat, (size_t)B * F * 8), o_df = h.add_out(dflat, (size_t)B * F * P * 8), o_st = h.add_out(status, (size_t)B * 4),
                o_ns = h.add_out(n_steps, (size_t)B * 8);
-  if ((rc = h.upload())) return rc;
-  rc = pk_solve_protein_sens_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<const double>(o_y0), y0_is_batched, h.dev<const double>(o_t), T, opts,
-                                   h.dev<double>(o_flat), h.dev<double>(o_df), h.dev<int32_t>(o_st), h.dev<int32_t>(o_ns));
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  return h.download();
+  return h.run([&] {
+    return pk_solve_protein_sens_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<const double>(o_y0), y0_is_batched, h.dev<const double>(o_t), T, opts,
+                                       h.dev<double>(o_flat), h.dev<double>(o_df), h.dev<int32_t>(o_st), h.dev<int32_t>(o_ns));
+  });
 }
 
 int pk_rhs_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y, double* dydt) {
@@ -533,10 +508,7 @@ int pk_rhs_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B, cons
   PK_HIP(c, hipSetDevice(c->device));
   HostCall h(c);
   const size_t o_th = h.add_in(theta, (size_t)B * P * 8), o_y = h.add_in(y, (size_t)B * S * 8), o_f = h.add_out(dydt, (size_t)B * S * 8);
-  if ((rc = h.upload())) return rc;
-  rc = pk_rhs_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<const double>(o_y), h.dev<double>(o_f));
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  return h.download();
+  return h.run([&] { return pk_rhs_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<const double>(o_y), h.dev<double>(o_f)); });
 }
 
 int pk_jacobian_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, double* J) {
@@ -551,10 +523,7 @@ int pk_jacobian_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B,
   PK_HIP(c, hipSetDevice(c->device));
   HostCall h(c);
   const size_t o_th = h.add_in(theta, (size_t)B * P * 8), o_J = h.add_out(J, (size_t)B * S * S * 8);
-  if ((rc = h.upload())) return rc;
-  rc = pk_jacobian_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<double>(o_J));
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  return h.download();
+  return h.run([&] { return pk_jacobian_protein_batch(c, model, n_sites, B, h.dev<const double>(o_th), h.dev<double>(o_J)); });
 }
 
 int pk_dist_sched_parse(const char* value) { return pk::dist_sched_parse(value); }
@@ -589,44 +558,3 @@ double pk_time_solve_protein_batch(pk_ctx* c, int iters, int model, int n_sites,
 }
 
 }  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ score_fit (a6)
-namespace pk {
-// One wave per candidate: residual r = |target - pred| / N ;  score = delta sum r^2 + alpha sqrt(mean r^2) + beta mean r
-//   + gamma var(r) + mu ||theta||_2 / len(theta)            (config/config.py:176-226)
-__global__ __launch_bounds__(256) void score_fit_kernel(const double* __restrict__ theta, const int P, const double* __restrict__ target,
-                                                        const double* __restrict__ pred, const int N, const long long B,
-                                                        const double alpha, const double beta, const double gamma, const double delta,
-                                                        const double mu, double* __restrict__ out) {
-  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const double* pb = pred + b * N;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = lane; k < N; k += 64) { const double r = fabs(target[k] - pb[k]) / (double)N; s1 += r; s2 = __builtin_fma(r, r, s2); }
-  double t2 = 0.0;
-  const double* tb = theta + b * P;
-  for (int k = lane; k < P; k += 64) t2 = __builtin_fma(tb[k], tb[k], t2);
-  for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); t2 += __shfl_xor(t2, off); }
-  const double mean = s1 / N;
-  // two-pass variance like np.var
-  double v = 0.0;
-  for (int k = lane; k < N; k += 64) { const double d = fabs(target[k] - pb[k]) / (double)N - mean; v = __builtin_fma(d, d, v); }
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  if (lane == 0) out[b] = delta * s2 + alpha * sqrt(s2 / N) + beta * mean + gamma * (v / N) + mu * (sqrt(t2) / P);
-}
-}  // namespace pk
-
-extern "C" int pk_score_fit_batch(pk_ctx* c, int64_t B, const double* theta, int P, const double* target, const double* pred, int N,
-                                  const double* weights, double* out) {
-  if (!c) return PK_ERR_ARG;
-  if (B < 0 || P < 1 || N < 1) return fail(c, PK_ERR_ARG, "B >= 0, P >= 1, N >= 1 required");
-  if (B == 0) return PK_OK;
-  if (!theta || !target || !pred || !out) return fail(c, PK_ERR_ARG, "null pointer");
-  const double a = weights ? weights[0] : 1.0, b = weights ? weights[1] : 1.0, g = weights ? weights[2] : 1.0, d = weights ? weights[3] : 1.0,
-               m = weights ? weights[4] : 1.0;
-  PK_HIP(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(pk::score_fit_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, theta, P, target, pred, N, (long long)B, a, b, g, d, m, out);
-  PK_HIP(c, hipGetLastError());
-  return PK_OK;
-}
