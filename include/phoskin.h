@@ -153,10 +153,14 @@ int pk_solve_protein_batch(pk_ctx*, int model, int n_sites, int64_t B,
  * factors of the state solve, differentiated stage by stage: csrc/pk_sens.hpp).  Replaces the 1 + P calls of models.solve_ode per Jacobian
  * that scipy.optimize.curve_fit's '2-point' differences make under paramest/normest.py:167-326 and paramest/toggle.py.
  *   flat [B,F]; dflat [B,F,P] (row-major: the P derivatives of one flat entry are contiguous); status / n_steps as above.
- * The derivative follows flat's own post-processing: 0 where the value was clipped at 0, scaled by 1 / y0 under opts->normalize.
+ * The derivative follows flat's own post-processing: scaled by 1 / y0 under opts->normalize, and 0 where the value was clipped at 0 -- where
+ * the state is below -atol, that is: a state within atol of 0 is not known to be negative (a site whose rate sits on the bound 0 decays to
+ * +-1e-24), so its value is clipped but its derivative row is kept; it is the row that can move the rate off the bound.
  * Tangents are held to the same rtol / atol as the states (maximum norm over all columns).  Method LRP12 only.
- * Sizes: pk_protein_sens_available(model, n_sites) != 0 -- distmod / succmod n_sites <= 62 (up to 14: one column per lane, csrc/pk_sens.hpp;
- * beyond: rows across the lanes, eight columns per lane, chunked columns, csrc/pk_sens_rows.hpp), randmod n_sites <= 7 (6 and 7: the
+ * Sizes: pk_protein_sens_available(model, n_sites) != 0 -- distmod / succmod n_sites <= 62 (one column per lane, csrc/pk_sens.hpp: exists up to 14, the
+ * default below the measured crossover, distmod n_sites < 10 and succmod n_sites < 6; from there on: rows across the lanes, eight columns
+ * per lane, chunked columns, csrc/pk_sens_rows.hpp -- PK_SENS_ROWS=2 keeps the column kernel up to 14, =1 takes the rows kernel at every
+ * size), randmod n_sites <= 7 (6 and 7: the
  * parity-eliminated inverse in registers serving eight columns per workgroup, csrc/pk_rand_sens.hpp); PK_ERR_UNSUPPORTED beyond (callers
  * difference pk_solve_protein_batch there, as phoskintime_amd.paramest.fit_rows_batch does).  Kernels that cut the columns of a replica
  * into chunks integrate the state once per chunk with its own step-size control: every column is within rtol / atol of the exact

@@ -302,6 +302,115 @@ def solve_exact_lti(model: int, params, init_cond, n_sites: int, t):
     return out
 
 
+def _augmented(model: int, params, n_sites: int, analytic: bool = False):
+    """Aug = [[M, b], [0, 0]] with d [y; 1] / dt = Aug [y; 1].  `analytic`: M from `jacobian_analytic` (O(S n) loops) instead of probing the
+    RHS column by column (O(S^2 n): 0.4 s at randmod n = 7); tests/test_oracle_golden.py pins the two to each other."""
+    if analytic:
+        M = jacobian_analytic(model, params, n_sites)
+        b = rhs(model, np.zeros(M.shape[0]), 0.0, params, n_sites)
+    else:
+        M, b = lti_matrix(model, params, n_sites)
+    S_ = M.shape[0]
+    Aug = np.zeros((S_ + 1, S_ + 1))
+    Aug[:S_, :S_] = M
+    Aug[:S_, S_] = b
+    return Aug
+
+
+def _one_blas_thread():
+    """Matrices of at most 130 rows: a threaded BLAS spends its time handing them out (10x at randmod n = 7).  Speed only."""
+    try:
+        from threadpoolctl import threadpool_limits
+    except ImportError:
+        from contextlib import nullcontext
+        return nullcontext()
+    return threadpool_limits(limits=1, user_api="blas")
+
+
+def sens_exact_lti(model: int, params, init_cond, n_sites: int, t, cols=None):
+    """Integrator-free parameter derivatives of `solve_exact_lti`'s solution, y0 held fixed: (sol [T, S], dsol [T, S, len(cols)]) with
+    dsol[k, :, j] = d y(t_k) / d theta_cols[j].  The models are affine in theta, so the direction of column c in the augmented matrix
+    Aug = [[M, b], [0, 0]] is exactly E_c = Aug(e_c) - Aug(0); interval by interval, with L the Frechet derivative of the matrix
+    exponential (scipy.linalg.expm_frechet, Al-Mohy & Higham 2009):
+        z_k = expm(Aug dt) z_{k-1},   z'_k = expm(Aug dt) z'_{k-1} + L(Aug dt, E_c dt) z_{k-1}.
+    No difference quotient, hence no step to choose: it holds for rates on a bound of the fit's box (0) and for rates spread over nine
+    decades, where a central difference of the solution does not."""
+    from scipy.linalg import expm_frechet
+    t = np.atleast_1d(np.asarray(t, dtype=float))
+    th = np.asarray(params, dtype=float)
+    cols = np.arange(th.size) if cols is None else np.asarray(cols, dtype=int)
+    Aug = _augmented(model, th, n_sites)
+    S_ = Aug.shape[0] - 1
+    Aug0 = _augmented(model, np.zeros(th.size), n_sites, analytic=True)
+    E = []
+    for c in cols:
+        e = np.zeros(th.size)
+        e[c] = 1.0
+        E.append(_augmented(model, e, n_sites, analytic=True) - Aug0)         # entries 0, +-1: exact
+    z = np.concatenate((np.asarray(init_cond, float), [1.0]))
+    dz = np.zeros((S_ + 1, cols.size))
+    sol = np.empty((t.size, S_))
+    dsol = np.zeros((t.size, S_, cols.size))
+    sol[0] = z[:S_]
+    with _one_blas_thread():
+        for k in range(1, t.size):
+            dt = t[k] - t[k - 1]
+            X = expm(Aug * dt)
+            dz = X @ dz
+            for j in range(cols.size):
+                dz[:, j] += expm_frechet(Aug * dt, E[j] * dt, compute_expm=False) @ z
+            z = X @ z
+            sol[k] = z[:S_]
+            dsol[k] = dz[:S_]
+    return sol, dsol
+
+
+def flat_and_jacobian(model: int, sol, dsol, init_cond, n_sites: int, clip_nonneg: bool = True, normalize: bool = False):
+    """(flat [F], dflat [F, C]) from (sol [T, S], dsol [T, S, C]) as include/phoskin.h defines them for pk_solve_protein_sens_batch: the
+    `flatten_observables` layout; value 0 and a zero derivative row where the clip is active (sol < 0); both scaled by 1 / y0 of the state
+    under `normalize`; zero rows at t0 (the initial values are data)."""
+    sol = np.array(sol, dtype=float)
+    dsol = np.array(dsol, dtype=float)
+    dsol[0] = 0.0
+    if clip_nonneg:
+        neg = sol < 0.0
+        sol[neg] = 0.0
+        dsol[neg] = 0.0
+    if normalize:
+        inv = 1.0 / np.asarray(init_cond, float)
+        sol = sol * inv[None, :]
+        dsol = dsol * inv[None, :, None]
+    flat = flatten_observables(model, sol, n_sites)
+    dflat = np.stack([flatten_observables(model, dsol[:, :, j], n_sites) for j in range(dsol.shape[2])], axis=1) if dsol.shape[2] else np.zeros((flat.size, 0))
+    return flat, dflat
+
+
+#: where the fits take the sensitivity kernels (paramest/multistart.py, build_free_bounds: distmod / succmod in [0, 20], randmod in log
+#: space between log 1e-8 and log 20) and one start the step controller can only pass by watching the tangents
+SENS_REGIMES = ("uniform", "loguniform", "zeros", "steady")
+
+
+def sens_regime(regime: str, model: int, n_sites: int, rng, B: int):
+    """(theta [B, P], y0 [S] or [B, S]) of one regime: "uniform" U(0, 20); "loguniform" 1e-8 .. 20; "zeros" U(0, 20) with 30 % of the
+    entries exactly 0 (variables on the lower bound of the box); "steady" U(2, 20) started AT the steady state of each theta, passed as
+    data -- the states do not move while the tangents have transients at rate ~ 20."""
+    P, S_ = n_params(model, n_sites), n_states(model, n_sites)
+    y0 = rng.uniform(0.3, 1.5, size=S_)
+    if regime == "uniform":
+        th = rng.uniform(0.0, 20.0, size=(B, P))
+    elif regime == "loguniform":
+        th = np.exp(rng.uniform(np.log(1e-8), np.log(20.0), size=(B, P)))
+    elif regime == "zeros":
+        th = rng.uniform(0.0, 20.0, size=(B, P))
+        th[rng.random((B, P)) < 0.3] = 0.0
+    elif regime == "steady":
+        th = rng.uniform(2.0, 20.0, size=(B, P))
+        y0 = np.stack([steady_state(model, th[b], n_sites) for b in range(B)])
+    else:
+        raise ValueError(regime)
+    return th, y0
+
+
 # --------------------------------------------------------------------- reductions
 def compute_Y(solution: np.ndarray, n_sites: int, metric: str = "total_signal") -> float:
     """sensitivity/analysis.py:90-176 (_compute_Y) with Y_METRIC as an argument -- loop for loop, in the reference's summation order

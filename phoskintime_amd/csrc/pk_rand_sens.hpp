@@ -104,7 +104,7 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA)
       const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
       if (fi < 0) continue;
       const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
-      const bool clipped = A.clip && (Y[row * KC] < 0.0);
+      const bool clipped = A.clip && (Y[row * KC] < (c == 0 ? 0.0 : -A.atol));      // derivative rows: negative beyond the absolute tolerance (pk_sens.hpp, emit)
       const double v = nan_fill ? __builtin_nan("") : (clipped ? 0.0 : Y[row * KC + c] * sc);
       if (c == 0) { if (ch == 0) fl[fi] = v; }
       else { const int p = pcol(c); if (p >= 0) dfl[(long long)fi * P + p] = v; }

@@ -565,7 +565,9 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const S
         const int fi = (i == 0) ? (k >= 5 ? k - 5 : -1) : (i == 1 ? T5 + k : T5 + T + (i - 2) * T + k);
         if (fi >= 0 && live) {
           const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
-          const bool clipped = A.clip && (by[i] < 0.0);
+          // the value is clipped below 0; its derivative is dropped only where the state is negative beyond the absolute tolerance: a state
+          // that has decayed to +-1e-24 (a rate on the bound 0) is not known to be negative, and its row is what moves the rate off the bound
+          const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
           double r;
           if (nan_fill) r = __builtin_nan("");
           else r = clipped ? 0.0 : y.template get<i>() * sc;

@@ -84,11 +84,12 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
     const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
     if (fi < 0) return;
     const bool clipped = A.clip && (y[0] < 0.0);
+    const bool dropped = A.clip && (y[0] < -A.atol);       // derivative rows: negative beyond the absolute tolerance (pk_sens.hpp, emit)
     const double qnan = __builtin_nan("");
     if (ch == 0) fl[fi] = nan_fill ? qnan : (clipped ? 0.0 : y[0] * yscale);
     static_for<KT>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
-      if (ch * KT + k < P) dfl[(long long)fi * P + k] = nan_fill ? qnan : (clipped ? 0.0 : y[1 + k] * yscale);
+      if (ch * KT + k < P) dfl[(long long)fi * P + k] = nan_fill ? qnan : (dropped ? 0.0 : y[1 + k] * yscale);
     });
   };
   auto fail_from = [&](int kk) {
@@ -221,7 +222,7 @@ static hipError_t launch_sens_rows_one(const SensArgs& a, hipStream_t st) {
 
 template <int MODEL>
 static hipError_t launch_sens_rows_model(const SensArgs& a, hipStream_t st) {
-  if (a.s.S <= 16) return launch_sens_rows_one<MODEL, 16>(a, st);      // only reached on request (PK_SENS_ROWS=1: A/B against pk_sens.hpp)
+  if (a.s.S <= 16) return launch_sens_rows_one<MODEL, 16>(a, st);      // distmod n = 10 .. 14, succmod n = 6 .. 14 by default; below on request (PK_SENS_ROWS=1)
   if (a.s.S <= 32) return launch_sens_rows_one<MODEL, 32>(a, st);
   return launch_sens_rows_one<MODEL, 64>(a, st);
 }

@@ -38,9 +38,12 @@ def _oracle_jac(model, th, y0, n, t):
     return np.stack(cols, axis=1)                      # [F, P]
 
 
-CASES = [("distmod", 1), ("distmod", 3), ("distmod", 4), ("distmod", 8), ("distmod", 13), ("distmod", 14),
-         ("succmod", 1), ("succmod", 2), ("succmod", 5), ("succmod", 9), ("succmod", 14),
-         # rows-per-lane kernel (csrc/pk_sens_rows.hpp): 32-lane groups up to 30 sites (BASELINE config 3's size), 64-lane groups to 62
+CASES = [# column-per-lane kernel (csrc/pk_sens.hpp): the default below distmod n = 10 / succmod n = 6 (launch_sens, pk_inst_sens_rand.hip)
+         ("distmod", 1), ("distmod", 3), ("distmod", 4), ("distmod", 8), ("succmod", 1), ("succmod", 2), ("succmod", 5),
+         # rows-per-lane kernel (csrc/pk_sens_rows.hpp) in 16-lane groups (S <= 16), the default from distmod n = 10 / succmod n = 6 on; the
+         # column kernel at these sizes (PK_SENS_ROWS=2) and the rows kernel below them (=1): tests/test_gpu_sens_regimes.py, forced kernels
+         ("distmod", 13), ("distmod", 14), ("succmod", 9), ("succmod", 14),
+         # the same kernel where it is the only one: 32-lane groups up to 30 sites (BASELINE config 3's size), 64-lane groups to 62
          ("distmod", 15), ("distmod", 30), ("distmod", 31), ("distmod", 62), ("succmod", 15), ("succmod", 30), ("succmod", 47), ("succmod", 62),
          ("randmod", 1), ("randmod", 2), ("randmod", 3), ("randmod", 4), ("randmod", 5),
          # parity-eliminated inverse serving eight columns per workgroup (csrc/pk_rand_sens.hpp): 74 / 139 columns of 65 / 129 rows
