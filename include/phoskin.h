@@ -171,6 +171,34 @@ int pk_solve_protein_sens_batch(pk_ctx*, int model, int n_sites, int64_t B,
                                 const double* t, int T, const pk_solver_opts* opts,
                                 double* flat, double* dflat, int32_t* status, int32_t* n_steps);
 
+/* The scalar Morris output m = _compute_Y (PK_METRIC_*, as pk_solve_protein_batch forms it) AND its gradient d m / d theta from ONE
+ * integration: the metric flavour of the output stage of the kernels behind pk_solve_protein_sens_batch.  The gradient cannot be rebuilt
+ * from dflat: the metric sums ALL observed rows i < 2 + n_sites at ALL T output times, and flat has no slot for the mRNA row at the first
+ * five times.
+ *   metric [B]; dmetric [B,P]; flat [B,F] | NULL; dflat [B,F,P] | NULL (NULL = not written: B (1 + P) doubles leave the kernel instead of
+ *   B F (1 + P)); status / n_steps as above.  All arrays are device pointers; the call is asynchronous on the context's stream.
+ * With v[i,k] the post-processed value of observed row i at output time k (clipped at 0 under opts->clip_nonneg, scaled by 1 / y0[i]
+ * under opts->normalize: exactly as flat), d[i,k,p] its post-processed derivative (scaled alike; 0 where the state is below -atol under
+ * clip_nonneg, the rule of dflat; 0 at k = 0, the initial values being data), L = T (2 + n_sites) and vbar the mean of v:
+ *   total_signal    g[p] = sum d
+ *   mean_activity   g[p] = sum d / L
+ *   variance        g[p] = (2 / L) sum (v - vbar) d      (accumulated as sum (v - c) d and sum d with c the mean at t0, never as the
+ *                                                         difference of the raw sums)
+ *   dynamics        g[p] = 2 sum_i sum_{k >= 1} (v[i,k] - v[i,k-1]) (d[i,k,p] - d[i,k-1,p])
+ *   l2_norm         g[p] = sum v d / m, and 0 where m = 0
+ * Failure follows dflat's NaN fill, the NaN entries entering the sums: a flagged replica has metric = NaN, and NaN in the columns of
+ * dmetric whose chunk was flagged (kernels that cut the columns into chunks: chunk 0 forms metric, every chunk integrates the state itself
+ * and forms its own columns; status is the OR over the chunks).  T = 1: metric is the metric of the post-processed y0, dmetric is 0.
+ * Same sizes (pk_protein_sens_available), options (LRP12 only) and kernel per size, PK_SENS_ROWS included, as pk_solve_protein_sens_batch,
+ * and PK_ERR_UNSUPPORTED in the same cases; PK_ERR_ARG for a metric_id outside PK_METRIC_* and for a null metric or dmetric.
+ * flat, dflat, status and n_steps are bit-equal to those of pk_solve_protein_sens_batch for the same inputs; metric and dmetric do not
+ * depend on whether flat and dflat were asked for, nor on the batch around a replica (every reduction runs in a fixed order). */
+int pk_solve_protein_sens_metric_batch(pk_ctx*, int model, int n_sites, int64_t B,
+                                       const double* theta, const double* y0, int y0_is_batched,
+                                       const double* t, int T, const pk_solver_opts* opts, int metric_id,
+                                       double* metric, double* dmetric, double* flat, double* dflat,
+                                       int32_t* status, int32_t* n_steps);
+
 /* Replaces models.{distmod,succmod}.ode_core / models.randmod.ode_system (distmod.py:7-65, succmod.py:9-90,
  * randmod.py:122-247) evaluated for a batch: y [B,S] -> dydt [B,S]. */
 int pk_rhs_protein_batch(pk_ctx*, int model, int n_sites, int64_t B,

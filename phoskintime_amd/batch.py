@@ -213,6 +213,65 @@ def solve_ode_sens_batch(model, theta: ArrayLike, init_cond: ArrayLike, num_psit
     return out
 
 
+@dataclass
+class SensMetricResult:
+    """Outputs of ``solve_ode_sens_metric_batch`` (tensors live on the GPU; ``None`` where not requested)."""
+    metric: torch.Tensor              # [B]        _compute_Y of the post-processed observables
+    dmetric: torch.Tensor             # [B, P]     d metric / d theta
+    flat: Optional[torch.Tensor]      # [B, F]
+    dflat: Optional[torch.Tensor]     # [B, F, P]
+    status: torch.Tensor              # [B] int32
+    n_steps: torch.Tensor             # [B, 2] int32
+
+
+def solve_ode_sens_metric_batch(model, theta: ArrayLike, init_cond: ArrayLike, num_psites: int, t: ArrayLike, *,
+                                metric: str = "total_signal", want_flat: bool = False, want_dflat: bool = False,
+                                rtol: Optional[float] = None, atol: Optional[float] = None, h0: Optional[float] = None,
+                                max_steps: Optional[int] = None, clip_nonneg: bool = True, normalize: bool = False,
+                                device: Optional[int] = None) -> SensMetricResult:
+    """The scalar Morris output ``Y = _compute_Y(sol)`` (``metric``: a key of ``_capi.METRICS``) AND its gradient d Y / d theta for B
+    parameter vectors from one launch: the kernels of ``solve_ode_sens_batch`` with the metric formed in their output stage
+    (include/phoskin.h, pk_solve_protein_sens_metric_batch, has the formulas and the clip / normalise / NaN rules).  ``flat`` / ``dflat``
+    are written only on request -- without them B (1 + P) doubles leave the kernel -- and are then bit-equal to ``solve_ode_sens_batch``'s.
+    Same sizes as ``solve_ode_sens_batch`` (``sens_available``); raises ``PhoskinError`` (PK_ERR_UNSUPPORTED) beyond."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {sorted(METRICS)}, got {metric!r}")
+    ctx = get_context(device)
+    dev = torch.device("cuda", ctx.device)
+    mid = model_id(model)
+    n = int(num_psites)
+    S, P = n_states(mid, n), n_params(mid, n)
+    th = _dev_f64(theta, dev)
+    if th.dim() == 1:
+        th = th.unsqueeze(0)
+    if th.dim() != 2 or th.shape[1] != P:
+        raise ValueError(f"theta must be [B, {P}] for model {mid} with {n} sites, got {tuple(th.shape)}")
+    B = th.shape[0]
+    y0 = _dev_f64(init_cond, dev)
+    if y0.shape == (S,):
+        batched = 0
+    elif y0.shape == (B, S):
+        batched = 1
+    else:
+        raise ValueError(f"init_cond must be [{S}] or [{B}, {S}], got {tuple(y0.shape)}")
+    tt = _dev_f64(np.atleast_1d(t) if not isinstance(t, torch.Tensor) else t, dev).reshape(-1)
+    T = tt.numel()
+    if T < 1:
+        raise ValueError("t must hold at least one time point")
+    F = flat_len(mid, n, T)
+    opts = default_opts(rtol=rtol, atol=atol, h0=h0, max_steps=max_steps, clip_nonneg=int(bool(clip_nonneg)), normalize=int(bool(normalize)))
+    out = SensMetricResult(metric=torch.empty((B,), dtype=torch.float64, device=dev), dmetric=torch.empty((B, P), dtype=torch.float64, device=dev),
+                           flat=torch.empty((B, F), dtype=torch.float64, device=dev) if want_flat else None,
+                           dflat=torch.empty((B, F, P), dtype=torch.float64, device=dev) if want_dflat else None,
+                           status=torch.zeros((B,), dtype=torch.int32, device=dev), n_steps=torch.zeros((B, 2), dtype=torch.int32, device=dev))
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.check(ctx.lib.pk_solve_protein_sens_metric_batch(ctx.handle, mid, n, B, _ptr(th), _ptr(y0), batched, _ptr(tt), T, C.byref(opts),
+                                                         METRICS[metric], _ptr(out.metric), _ptr(out.dmetric), _ptr(out.flat), _ptr(out.dflat),
+                                                         _ptr(out.status), _ptr(out.n_steps)))
+    out._keepalive = (th, y0, tt)  # type: ignore[attr-defined]
+    return out
+
+
 def rhs_batch(model, theta: ArrayLike, y: ArrayLike, num_psites: int, device: Optional[int] = None) -> torch.Tensor:
     """dy/dt for B (theta, y) pairs: reference ``ode_core`` / ``ode_system`` batched.  Returns [B, S] on the GPU."""
     ctx = get_context(device)

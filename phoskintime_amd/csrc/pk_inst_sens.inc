@@ -4,18 +4,20 @@
 
 namespace pk {
 
-template <class Sys, int GP>
-static hipError_t launch_sens_one(const SensArgs& a, hipStream_t st) {
+template <class Sys, int GP, class Args>
+static hipError_t launch_sens_one(const Args& a, hipStream_t st) {
   constexpr int NG = 64 / GP;
+  constexpr bool MET = sens_metric_flavour<Args>();
   const long long nblk = (a.s.B + NG - 1) / NG;
-  constexpr size_t lds = sens_lds_bytes<Sys, GP>();
-  static_assert(lds <= 64 * 1024, "fits the default dynamic-LDS limit");
-  hipLaunchKernelGGL((sens_kernel<Sys, GP>), dim3((unsigned)nblk), dim3(64), lds, st, a);
+  static_assert(sens_metric_lds_bytes<Sys, GP>(true) <= 64 * 1024, "fits the default dynamic-LDS limit");
+  size_t lds = sens_lds_bytes<Sys, GP>();
+  if constexpr (MET) lds = sens_metric_lds_bytes<Sys, GP>(a.s.metric_id == PK_METRIC_DYNAMICS);
+  hipLaunchKernelGGL((sens_kernel<Sys, GP, Args>), dim3((unsigned)nblk), dim3(64), lds, st, a);
   return hipGetLastError();
 }
 
-template <int MODEL>
-static hipError_t launch_sens_chain(const SensArgs& a, hipStream_t st) {
+template <int MODEL, class Args>
+static hipError_t launch_sens_chain(const Args& a, hipStream_t st) {
   const int n = a.s.n_sites;                                 // columns: 1 + P = 5 + 2 n
   if (n <= 1) return launch_sens_one<ChainSys<MODEL, 1>, 8>(a, st);
   if (n <= 3) return launch_sens_one<ChainSys<MODEL, 3>, 16>(a, st);

@@ -16,7 +16,8 @@ bool sens_available(int model, int n_sites) {
   return n_sites <= 62;
 }
 
-hipError_t launch_sens(const SensArgs& a, int model, hipStream_t st) {
+// true where the rows-per-lane kernel (pk_sens_rows.hpp) takes a chain model: the one place that reads the switches, for both flavours
+bool sens_takes_rows(int model, int n_sites) {
   // PK_SENS_ROWS=1 (read once): the rows-per-lane kernel at every size -- the A/B switch the tests use to hold the two kernels to agreement
   static const int rows_env = [] { const char* v = getenv("PK_SENS_ROWS"); return v ? atoi(v) : 0; }();
   // PK_SENS_ROWS_MIN (dev, read once): smallest size the rows-per-lane kernel takes by default
@@ -24,7 +25,11 @@ hipError_t launch_sens(const SensArgs& a, int model, hipStream_t st) {
   // 6.5, n = 14: 7.2 vs 4.3 (B = 16 384);  succmod n = 4: 1.5 vs 3.1, n = 6: 5.0 vs 4.6, n = 10: 8.5 vs 6.2, n = 14: 8.1 vs 4.7 (B = 16 384)
   static const int rows_min_env = [] { const char* v = getenv("PK_SENS_ROWS_MIN"); return v ? atoi(v) : 0; }();
   const int rows_min = rows_min_env > 0 ? rows_min_env : (model == M_DIST ? 10 : 6);
-  if (model != M_RAND && (a.s.n_sites > 14 || rows_env == 1 || (rows_env != 2 && a.s.n_sites >= rows_min))) return model == M_DIST ? launch_sens_rows_dist(a, st) : launch_sens_rows_succ(a, st);
+  return model != M_RAND && (n_sites > 14 || rows_env == 1 || (rows_env != 2 && n_sites >= rows_min));
+}
+
+hipError_t launch_sens(const SensArgs& a, int model, hipStream_t st) {
+  if (sens_takes_rows(model, a.s.n_sites)) return model == M_DIST ? launch_sens_rows_dist(a, st) : launch_sens_rows_succ(a, st);
   if (model == M_DIST) return launch_sens_dist(a, st);
   if (model == M_SUCC) return launch_sens_succ(a, st);
   const int n = a.s.n_sites;

@@ -74,7 +74,8 @@ hipError_t launch_rand_parity(const SolveArgs& a, hipStream_t st, bool pinned_fa
 }
 
 // forward sensitivities of randmod n = 6, 7: the parity-eliminated inverse serves eight columns per workgroup (pk_rand_sens.hpp)
-hipError_t launch_rand_sens(const SensArgs& a, hipStream_t st) {
+template <class Args>
+static hipError_t launch_rand_sens_any(const Args& a, hipStream_t st) {
   // n = 6: one wave per column chunk (8 x 8 lanes, 4 x 4 blocks; 34.7 against 44.5 ms per 1 024 Jacobians on the 256-thread grid, same box).
   // PK_RAND_SENS6_TB=16 (dev, read once): the 256-thread grid
   static const int tb6 = [] { const char* v = getenv("PK_RAND_SENS6_TB"); return v ? atoi(v) : 8; }();
@@ -82,6 +83,10 @@ hipError_t launch_rand_sens(const SensArgs& a, hipStream_t st) {
   if (a.s.n_sites == 7) return launch_rand_sens_one<7>(a, st);
   return hipErrorInvalidValue;
 }
+hipError_t launch_rand_sens(const SensArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
+// its metric flavour (pk_sens.hpp, SensMetricArgs).  Here and not beside the other metric instantiations: pk_wide.hpp, which pk_rand_sens.hpp
+// builds on, defines kernels that one translation unit alone may hold
+hipError_t launch_rand_sens_metric(const SensMetricArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
 
 bool rand_dense_available(int n_sites) {
   static const bool on = [] { const char* v = getenv("PK_WIDE_RAND_DENSE"); return !(v && v[0] == '0'); }();

@@ -31,8 +31,10 @@ __host__ __device__ constexpr size_t rand_sens_lds_bytes(int n) {
 }
 
 // TBP: side of the thread grid over the even Schur complement: 16 (256 threads) or 8 (n = 6: ONE wave per column chunk, 4 x 4 blocks per lane)
-template <int NB, int TBP = 16>
-__global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA) {
+// Args = SensArgs, or SensMetricArgs (pk_sens.hpp) for the metric flavour of the output stage
+template <int NB, int TBP = 16, class Args = SensArgs>
+__global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const Args SA) {
+  constexpr bool MET = sens_metric_flavour<Args>();
   static_assert((NB == 6 || NB == 7) && (TBP == 16 || TBP == 8) && (1 << NB) <= TBP * TBP, "thread grid over the even Schur complement");
   using Tab = ResolventTab<PK_METHOD_LRP12>;
   constexpr int NALL = 1 << NB, NM = NALL / 2, TB = TBP, TS = NM / TB, NT = TB * TB, KC = kRandSensKC, KT = KC - 1, S = NALL + 1;
@@ -98,7 +100,41 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA)
   const int T5 = T > 5 ? T - 5 : 0;
   double* const fl = A.flat + rep * F;
   double* const dfl = SA.dflat + rep * (long long)F * P;
+  // metric flavour: thread it < NIT owns the (observed row, column) item it = row KC + c: its two sums (metric_acc), and the state value
+  // and the column's entry at the previous output time, stay in its registers (no LDS beyond the plain flavour's: the workgroups per CU
+  // are bounded by LDS here); mC = the shift, formed by every thread for itself
+  constexpr int NIT = (2 + NB) * KC;
+  static_assert(NIT <= NT, "one output item per thread");
+  double mA = 0.0, mB = 0.0, mV = 0.0, mR = 0.0, mC = 0.0;
   auto emit = [&](const int k, const bool nan_fill) __attribute__((always_inline)) {
+    if constexpr (MET) {                                          // every observed row enters the sums, the mRNA row at k < 5 (fi < 0) too
+      auto post = [&](const int row) __attribute__((always_inline)) {
+        const double yv = Y[row * KC];
+        return (A.clip && yv < 0.0) ? 0.0 : yv * (A.normalize ? 1.0 / y0p[row] : 1.0);
+      };
+      if (k == 0) {
+        double s0 = 0.0;
+        for (int row = 0; row < 2 + NB; ++row) s0 += post(row);
+        mC = s0 / (double)(2 + NB);
+      }
+      if (tid < NIT) {
+        const int row = tid / KC, c = tid % KC;
+        const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
+        const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
+        const double qnan = __builtin_nan("");
+        const double sv = nan_fill ? qnan : post(row);
+        const bool clipped = A.clip && (Y[row * KC] < (c == 0 ? 0.0 : -A.atol));
+        const double v = nan_fill ? qnan : (clipped ? 0.0 : Y[row * KC + c] * sc);
+        const int p = pcol(c);
+        if (fi >= 0) {
+          if (c == 0) { if (ch == 0 && A.flat) fl[fi] = v; }
+          else if (p >= 0 && SA.dflat) dfl[(long long)fi * P + p] = v;
+        }
+        metric_acc(A.metric_id, c == 0, k, metric_weight(A.metric_id, k, sv, mV, mC), v, mR, mA, mB);
+        mV = sv; mR = v;
+      }
+      return;
+    }
     for (int it = tid; it < (2 + NB) * KC; it += nt) {
       const int row = it / KC, c = it % KC;
       const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
@@ -111,6 +147,21 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA)
     }
   };
   auto finish = [&](const int status, const int acc, const int rej) __attribute__((always_inline)) {
+    if constexpr (MET) {                                          // across the workgroup through LDS (the error vector's, idle here): thread c sums column c over the rows, in row order
+      double* const sA = ER; double* const sB = ER + NIT;
+      __syncthreads();
+      if (tid < NIT) { sA[tid] = mA; sB[tid] = mB; }
+      __syncthreads();
+      if (tid < KC) {
+        const int c = tid, p = pcol(c);
+        const double L = (double)T * (double)(2 + NB);
+        double a0 = 0.0, b0 = 0.0, a = 0.0, b = 0.0;
+        for (int row = 0; row < 2 + NB; ++row) { a0 += sA[row * KC]; b0 += sB[row * KC]; a += sA[row * KC + c]; b += sB[row * KC + c]; }
+        const double m = metric_value(A.metric_id, a0, b0, mC, L);
+        if (c == 0) { if (ch == 0) A.metric[rep] = m; }
+        else if (p >= 0) SA.dmetric[rep * P + p] = metric_grad(A.metric_id, a, b, a0, m, mC, L);
+      }
+    }
     if (tid != 0) return;
     if (A.status && status) atomicOr(&A.status[rep], status);            // zeroed by the launcher
     if (ch == 0 && A.n_steps) { A.n_steps[2 * rep] = acc; A.n_steps[2 * rep + 1] = rej; }
@@ -352,8 +403,8 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const SensArgs SA)
   finish(status, nacc, nrej);
 }
 
-template <int NB, int TBP = 16>
-static hipError_t launch_rand_sens_one(const SensArgs& a, hipStream_t st) {
+template <int NB, int TBP = 16, class Args = SensArgs>
+static hipError_t launch_rand_sens_one(const Args& a, hipStream_t st) {
   constexpr int KT = kRandSensKC - 1;
   const long long nch = (a.s.P + KT - 1) / KT, nblk = a.s.B * nch;
   if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -361,9 +412,9 @@ static hipError_t launch_rand_sens_one(const SensArgs& a, hipStream_t st) {
     hipError_t e = hipMemsetAsync(a.s.status, 0, (size_t)a.s.B * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
   }
-  constexpr size_t lds = rand_sens_lds_bytes(NB);
+  constexpr size_t lds = rand_sens_lds_bytes(NB);                      // both flavours
   static_assert(lds <= 64 * 1024, "fits the default dynamic-LDS limit");
-  hipLaunchKernelGGL((rand_sens_kernel<NB, TBP>), dim3((unsigned)nblk), dim3(TBP * TBP), lds, st, a);
+  hipLaunchKernelGGL((rand_sens_kernel<NB, TBP, Args>), dim3((unsigned)nblk), dim3(TBP * TBP), lds, st, a);
   return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 // sequence is therefore shared by the group; clipping (y < 0 -> 0) zeroes the derivative like it zeroes the value.
 // One wave per workgroup, NG = 64 / GP replicas per wave; LDS: two thread-private coefficient sets + 2 S doubles per group.
 #pragma once
+#include <type_traits>
 #include "pk_solve_kernel.hpp"
 
 namespace pk {
@@ -26,6 +27,61 @@ struct SensArgs {
   SolveArgs s;
   double* dflat;        // [B, F, P]
 };
+
+// The metric flavour of the output stage (a compile-time flavour selected by the argument type, as NetScore selects the scoring flavours
+// of net_rosw_solve): besides flat / dflat -- both optional here, null = not written -- the kernels return the scalar Morris output
+// m = _compute_Y of the post-processed observables (s.metric [B], s.metric_id; Emitter::finish in pk_solve_kernel.hpp defines it) and its
+// gradient d m / d theta (dmetric [B, P]).  The sums run over ALL observed rows i < 2 + n_sites at ALL output times, the mRNA row at
+// k < 5 included, which has no slot in flat.
+struct SensMetricArgs {
+  SolveArgs s;
+  double* dflat;        // [B, F, P] | null
+  double* dmetric;      // [B, P]
+};
+template <class Args> constexpr bool sens_metric_flavour() { return std::is_same<Args, SensMetricArgs>::value; }
+
+// One (row, output time) entry of the metric sums.  v: the post-processed state value, pv: the same at the previous output time, c: the
+// mean of v at t0 (the shift of Emitter::emit).  Every column keeps a = sum r and b = sum w x over the entries, r being the column's
+// entry (v itself in the state column, the post-processed tangent otherwise) and pr its value at the previous output time:
+//   variance   w = v - c,        x = r  (v - c in the state column: b = sum (v - c)^2)
+//   dynamics   w = v_k - v_k-1,  x = r_k - r_k-1  (nothing at k = 0)
+//   l2_norm    w = v,            x = r
+// The weight is the same for every column of a row: formed once per row and output time.
+__device__ __forceinline__ double metric_weight(const int metric_id, const int k, const double v, const double pv, const double c) {
+  switch (metric_id) {
+    case PK_METRIC_VARIANCE: return v - c;
+    case PK_METRIC_DYNAMICS: return k == 0 ? 0.0 : v - pv;
+    default: return v;
+  }
+}
+__device__ __forceinline__ void metric_acc(const int metric_id, const bool state_col, const int k, const double w, const double r, const double pr,
+                                           double& a, double& b) {
+  a += r;
+  double x = r;
+  if (metric_id == PK_METRIC_DYNAMICS) x = k == 0 ? 0.0 : r - pr;
+  else if (metric_id == PK_METRIC_VARIANCE && state_col) x = w;
+  b = __builtin_fma(w, x, b);
+}
+// m from the state column's sums (L = T (2 + n_sites) entries), and d m / d theta_p from a tangent column's (a0 = the state column's sum v)
+__device__ __forceinline__ double metric_value(const int metric_id, const double a, const double b, const double c, const double L) {
+  switch (metric_id) {
+    case PK_METRIC_TOTAL_SIGNAL: return a;
+    case PK_METRIC_MEAN_ACTIVITY: return a / L;
+    case PK_METRIC_VARIANCE: { const double ms = a / L - c; return b / L - ms * ms; }      // E[(v-c)^2] - (E[v-c])^2
+    case PK_METRIC_DYNAMICS: return b;
+    default: return sqrt(b);
+  }
+}
+__device__ __forceinline__ double metric_grad(const int metric_id, const double a, const double b, const double a0, const double m, const double c,
+                                              const double L) {
+  switch (metric_id) {
+    case PK_METRIC_TOTAL_SIGNAL: return a;
+    case PK_METRIC_MEAN_ACTIVITY: return a / L;
+    case PK_METRIC_VARIANCE: return (2.0 / L) * __builtin_fma(-(a0 / L - c), a, b);        // (2/L) sum (v - mean) d, from the shifted sums
+    case PK_METRIC_DYNAMICS: return 2.0 * b;
+    default: return m == 0.0 ? 0.0 : b / m;
+  }
+}
 
 // LDS pointers carry their address space explicitly: a pointer that has been through a struct member or a select otherwise degrades to
 // a generic one, and its loads / stores to `flat_*` instructions (measured on the first version of the cube kernels: 7x slower)
@@ -50,6 +106,7 @@ template <int MODEL, int NS>
 struct ChainSys {
   static_assert(MODEL == M_DIST || MODEL == M_SUCC, "chain systems");
   static constexpr int NR = NS + 2;
+  static constexpr int NOBS = NR;                                      // observed rows (i < 2 + n_sites): all of them
   static constexpr int NCOEF = 2 * NR + 1;
   static constexpr int K_C1 = 0, K_DG = NR, K_A = 2 * NR;
   static constexpr int MIN_WAVES = NS <= 3 ? 3 : NS <= 9 ? 2 : 1;      // measured: a third wave at NS = 5 costs spills and time
@@ -189,6 +246,7 @@ template <int NB>
 struct CubeSys {
   static constexpr int NM = 1 << NB;
   static constexpr int NR = NM + 1;
+  static constexpr int NOBS = 2 + NB;                                   // observed rows: R, P and the masks 1 .. n
   static constexpr int NCOEF = 2 * NM + 3;
   static constexpr int MIN_WAVES = NB <= 2 ? 3 : 1;                     // NB = 3 holds the 8 x 8 inverse in registers
   static constexpr int K_DG = 0, K_CI = NM, K_A = 2 * NM, K_B = 2 * NM + 1, K_C = 2 * NM + 2;
@@ -323,7 +381,7 @@ struct CubeSys {
 // few registers (one bit / one nibble per row); the coefficients of theta live once per group in LDS.
 template <int NB, int GP_>
 struct CubeLdsSys {
-  static constexpr int NM = 1 << NB, NR = NM + 1, GP = GP_;
+  static constexpr int NM = 1 << NB, NR = NM + 1, GP = GP_, NOBS = 2 + NB;
   static constexpr int MIN_WAVES = 1;
   static_assert(GP >= NM, "one lane per matrix row in the pivot-row / pivot-column update");
   static constexpr int GD = NM * NM + 2 * NM + 4;               // per group: inverse, dg[NM], ci[NM], cA cB cC (+ pad)
@@ -521,8 +579,16 @@ template <class Sys, int GP> constexpr size_t sens_lds_bytes() {
 // busy 38 % of the time: profiles/r02_g_sens_*), so the small systems trade registers for a second / third resident wave
 template <class Sys> constexpr int sens_min_waves() { return Sys::MIN_WAVES; }
 
-template <class Sys, int GP>
-__global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const SensArgs SA) {
+// the metric flavour: as sens_lds_bytes, and for PK_METRIC_DYNAMICS the previous output time's post-processed state values (per group)
+// and entries of every lane's own column (thread-private slots) behind it
+template <class Sys, int GP> constexpr size_t sens_metric_lds_bytes(bool dynamics) {
+  return sens_lds_bytes<Sys, GP>() + (dynamics ? ((size_t)(64 / GP) * Sys::NOBS + (size_t)Sys::NOBS * 64) * sizeof(double) : 0);
+}
+
+// Args = SensArgs, or SensMetricArgs for the metric flavour of the output stage (s.metric / dmetric required, s.flat / dflat optional)
+template <class Sys, int GP, class Args = SensArgs>
+__global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const Args SA) {
+  constexpr bool MET = sens_metric_flavour<Args>();
   using Tab = ResolventTab<PK_METHOD_LRP12>;
   constexpr int NR = Sys::NR, NG = 64 / GP;
   const SolveArgs& A = SA.s;
@@ -558,26 +624,75 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const S
   const int T5 = T > 5 ? T - 5 : 0;
   double* const fl = A.flat + rep * F;
   double* const dfl = SA.dflat + rep * (long long)F * P + (c - 1);
+  // metric flavour: this column's sums (metric_acc) and the shift; bpv = the group's post-processed state values at the previous output
+  // time, prs = this lane's own entries there -- read by `dynamics` alone, and only a launch for that metric carries their LDS
+  // (sens_metric_lds_bytes): the waves per CU of these kernels are bounded by LDS at several sizes
+  constexpr int NOBS = Sys::NOBS;
+  const bool dyn = MET && A.metric_id == PK_METRIC_DYNAMICS;
+  double mA = 0.0, mB = 0.0, mC = 0.0;
+  lds_f64* const bpv = lds0 + Sys::lds_doubles(NG) + NG * 2 * NR + (CL ? (size_t)2 * NR * 64 : 0) + g * NOBS;
+  lds_f64* const prs = lds0 + Sys::lds_doubles(NG) + NG * 2 * NR + (CL ? (size_t)2 * NR * 64 : 0) + NG * NOBS + lane;
   auto emit = [&](const int k, const bool nan_fill) __attribute__((always_inline)) {
+    if constexpr (MET) {
+      if (k == 0) {                                             // the mean of the post-processed initial values, in row order
+        double s0 = 0.0;
+        static_for<NOBS>([&](auto ic) {
+          constexpr int i = decltype(ic)::value;
+          if (i < S && i < 2 + n) s0 += (A.clip && by[i] < 0.0) ? 0.0 : by[i] * (A.normalize ? 1.0 / y0p[i] : 1.0);
+        });
+        mC = s0 / (double)(2 + n);
+      }
+    }
     static_for<NR>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       if (i < S && i < 2 + n) {
         const int fi = (i == 0) ? (k >= 5 ? k - 5 : -1) : (i == 1 ? T5 + k : T5 + T + (i - 2) * T + k);
-        if (fi >= 0 && live) {
+        if constexpr (!MET) {
+          if (fi >= 0 && live) {
+            const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
+            // the value is clipped below 0; its derivative is dropped only where the state is negative beyond the absolute tolerance: a state
+            // that has decayed to +-1e-24 (a rate on the bound 0) is not known to be negative, and its row is what moves the rate off the bound
+            const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
+            double r;
+            if (nan_fill) r = __builtin_nan("");
+            else r = clipped ? 0.0 : y.template get<i>() * sc;
+            if (is_base) fl[fi] = r;
+            else if (is_tan) dfl[(long long)fi * P] = r;
+          }
+        } else if constexpr (i < NOBS) {                        // every observed row enters the sums, the mRNA row at k < 5 (fi < 0) too
           const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
-          // the value is clipped below 0; its derivative is dropped only where the state is negative beyond the absolute tolerance: a state
-          // that has decayed to +-1e-24 (a rate on the bound 0) is not known to be negative, and its row is what moves the rate off the bound
+          const double qnan = __builtin_nan("");
+          const double v = nan_fill ? qnan : ((A.clip && by[i] < 0.0) ? 0.0 : by[i] * sc);
           const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
           double r;
-          if (nan_fill) r = __builtin_nan("");
+          if (nan_fill) r = qnan;
           else r = clipped ? 0.0 : y.template get<i>() * sc;
-          if (is_base) fl[fi] = r;
-          else if (is_tan) dfl[(long long)fi * P] = r;
+          if (fi >= 0 && live) {
+            if (is_base) { if (A.flat) fl[fi] = r; }
+            else if (is_tan && SA.dflat) dfl[(long long)fi * P] = r;
+          }
+          const double w = metric_weight(A.metric_id, k, v, dyn ? (double)bpv[i] : 0.0, mC);
+          metric_acc(A.metric_id, is_base, k, w, r, dyn ? (double)prs[i * 64] : 0.0, mA, mB);
+          if (dyn) prs[i * 64] = r;
         }
       }
     });
+    if constexpr (MET) if (dyn) {
+      wave_sync_lds();                                          // every lane has read the previous values
+      if (is_base) static_for<NOBS>([&](auto ic) { constexpr int i = decltype(ic)::value; bpv[i] = prs[i * 64]; });
+      wave_sync_lds();
+    }
   };
   auto finish = [&](const int status, const int acc, const int rej) {
+    if constexpr (MET) {                                        // in-lane sums: one store per lane
+      const double L = (double)T * (double)(2 + n);
+      const double a0 = bcast<GP, 0>(mA), b0 = bcast<GP, 0>(mB);
+      const double m = metric_value(A.metric_id, a0, b0, mC, L);
+      if (live) {
+        if (is_base) A.metric[rep] = m;
+        else if (is_tan) SA.dmetric[rep * P + (c - 1)] = metric_grad(A.metric_id, mA, mB, a0, m, mC, L);
+      }
+    }
     if (is_base && live) {
       if (A.status) A.status[rep] = status;
       if (A.n_steps) { A.n_steps[2 * rep] = acc; A.n_steps[2 * rep + 1] = rej; }

@@ -44,8 +44,10 @@ __device__ __forceinline__ void row_coef_deriv(const int p, const int n, const i
   }
 }
 
-template <int MODEL, int G, int KC>
-__global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
+// Args = SensArgs, or SensMetricArgs (pk_sens.hpp) for the metric flavour of the output stage
+template <int MODEL, int G, int KC, class Args = SensArgs>
+__global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
+  constexpr bool MET = sens_metric_flavour<Args>();
   using Tab = ResolventTab<PK_METHOD_LRP12>;
   using Solver = typename SolverFor<MODEL, G, true>::type;
   constexpr int WPB = 256 / G, KT = KC - 1;
@@ -79,7 +81,43 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
   const double yscale = (A.normalize && row < S) ? 1.0 / y_init : 1.0;
   double* const fl = A.flat + rep * F;
   double* const dfl = SA.dflat + rep * (long long)F * P + (long long)ch * KT;
+  // metric flavour: the sums of this lane's row for the state column (index 0) and its KT tangents and the row's entries at the previous
+  // output time live in thread-private LDS slots (3 KC per thread, touched only at the output times: the step loop keeps its registers
+  // and its two waves per SIMD); mC = the shift
+  extern __shared__ __align__(16) double sens_rows_lds[];
+  lds_f64* const ms = (lds_f64*)sens_rows_lds + threadIdx.x;
+  auto slotA = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[k * 256]; };
+  auto slotB = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[(KC + k) * 256]; };
+  auto slotP = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[(2 * KC + k) * 256]; };
+  double mC = 0.0;
+  if constexpr (MET) static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = 0.0; slotB(k) = 0.0; slotP(k) = 0.0; });
   auto emit = [&](const int kk, const bool nan_fill) {
+    if constexpr (MET) {                                   // every observed row enters the sums, the mRNA row at kk < 5 (fi < 0) too
+      const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
+      const bool clipped = A.clip && (y[0] < 0.0);
+      const bool dropped = A.clip && (y[0] < -A.atol);
+      const double qnan = __builtin_nan("");
+      const double v = nan_fill ? qnan : (clipped ? 0.0 : y[0] * yscale);
+      if (kk == 0) mC = gsum<G>(observed ? v : 0.0, lane) / (double)(2 + n);       // called once, before the step loop: the whole group is here
+      if (!observed) return;
+      if (fi >= 0 && ch == 0 && A.flat) fl[fi] = v;
+      const bool dyn = A.metric_id == PK_METRIC_DYNAMICS;      // the only metric that reads the previous output time's entries
+      const double pv = dyn ? (double)slotP(0) : 0.0;
+      const double w = metric_weight(A.metric_id, kk, v, pv, mC);
+      double sa[KC], sb[KC];                                 // all slots first: their latencies overlap
+      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; sa[k] = slotA(k); sb[k] = slotB(k); });
+      static_for<KT>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const double d = nan_fill ? qnan : (dropped ? 0.0 : y[1 + k] * yscale);
+        if (fi >= 0 && SA.dflat && ch * KT + k < P) dfl[(long long)fi * P + k] = d;
+        metric_acc(A.metric_id, false, kk, w, d, dyn ? (double)slotP(1 + k) : 0.0, sa[1 + k], sb[1 + k]);
+        if (dyn) slotP(1 + k) = d;
+      });
+      metric_acc(A.metric_id, true, kk, w, v, pv, sa[0], sb[0]);
+      if (dyn) slotP(0) = v;
+      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = sa[k]; slotB(k) = sb[k]; });
+      return;
+    }
     if (!observed) return;
     const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
     if (fi < 0) return;
@@ -97,6 +135,17 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
     for (; kk < T; ++kk) emit(kk, true);
   };
   auto finish = [&](const int status, const int acc, const int rej) {
+    if constexpr (MET) {                                   // across the G lanes of the group, column by column (rows beyond the observed ones hold zeros)
+      const double L = (double)T * (double)(2 + n);
+      const double a0 = gsum<G>(slotA(0), lane), b0 = gsum<G>(slotB(0), lane);
+      const double m = metric_value(A.metric_id, a0, b0, mC, L);
+      static_for<KT>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const double a = gsum<G>(slotA(1 + k), lane), b = gsum<G>(slotB(1 + k), lane);
+        if (row == 0 && ch * KT + k < P) SA.dmetric[rep * P + ch * KT + k] = metric_grad(A.metric_id, a, b, a0, m, mC, L);
+      });
+      if (row == 0 && ch == 0) A.metric[rep] = m;
+    }
     if (row != 0) return;
     if (A.status && status) atomicOr(&A.status[rep], status);          // zeroed by the launcher: a failure in ANY chunk flags the replica
     if (ch == 0 && A.n_steps) { A.n_steps[2 * rep] = acc; A.n_steps[2 * rep + 1] = rej; }
@@ -205,8 +254,8 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const SensArgs SA) {
 
 constexpr int kSensRowsKC = 8;                             // 1 state + 7 tangent columns per lane
 
-template <int MODEL, int G>
-static hipError_t launch_sens_rows_one(const SensArgs& a, hipStream_t st) {
+template <int MODEL, int G, class Args>
+static hipError_t launch_sens_rows_one(const Args& a, hipStream_t st) {
   constexpr int KT = kSensRowsKC - 1;
   const long long nch = (a.s.P + KT - 1) / KT;
   const long long items = a.s.B * nch, wpb = 256 / G;
@@ -216,12 +265,13 @@ static hipError_t launch_sens_rows_one(const SensArgs& a, hipStream_t st) {
     hipError_t e = hipMemsetAsync(a.s.status, 0, (size_t)a.s.B * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((sens_rows_kernel<MODEL, G, kSensRowsKC>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+  constexpr size_t lds = sens_metric_flavour<Args>() ? (size_t)3 * kSensRowsKC * 256 * sizeof(double) : 0;      // the metric flavour's slots
+  hipLaunchKernelGGL((sens_rows_kernel<MODEL, G, kSensRowsKC, Args>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
-template <int MODEL>
-static hipError_t launch_sens_rows_model(const SensArgs& a, hipStream_t st) {
+template <int MODEL, class Args>
+static hipError_t launch_sens_rows_model(const Args& a, hipStream_t st) {
   if (a.s.S <= 16) return launch_sens_rows_one<MODEL, 16>(a, st);      // distmod n = 10 .. 14, succmod n = 6 .. 14 by default; below on request (PK_SENS_ROWS=1)
   if (a.s.S <= 32) return launch_sens_rows_one<MODEL, 32>(a, st);
   return launch_sens_rows_one<MODEL, 64>(a, st);

@@ -6,6 +6,8 @@
                                                                           on the GPU, fused into the solve kernel)
   _perturb_solve                       sensitivity/analysis.py:178-195  (the pool worker: one parameter set -> (i, sol, flat, Y))
   _sensitivity_analysis                sensitivity/analysis.py:197-331  (reference argument list; returns (Si, best_trajectories))
+  local_sensitivity_batch              not in the reference: dY / d theta at B parameter vectors from ONE launch (forward sensitivities
+                                       with _compute_Y formed in the kernels' output stage), with elasticities and box-scaled slopes
   sensitivity_analysis_batch           the numerical core of _sensitivity_analysis: sample -> N*(D+1) solves + Y in
                                        ONE launch -> analyze -> RMSE ranking against data -> best K curves (no plotting)
 """
@@ -132,6 +134,37 @@ def sensitivity_analysis_batch(popt: Sequence[float], time_points, num_psites: i
             out["rmse"] = rmse
             out["best_idx"] = np.argsort(rmse)[:K]
     return out
+
+
+def local_sensitivity_batch(theta, time_points, num_psites: int, init_cond, model: Optional[str] = None, metric: Optional[str] = None,
+                            perturbation: Optional[float] = None, **solver_kw) -> Dict:
+    """Local sensitivities of the Morris output ``Y = _compute_Y(sol)`` at B parameter vectors (``theta`` [B, P]; a 1-D ``theta`` is one
+    row) from ONE launch of ``batch.solve_ode_sens_metric_batch`` -- exact derivatives of the discrete solution, where differencing takes
+    1 + P solves per vector and a Morris design N (D + 1).  Returns a dict with
+
+      names       parameter names (``define_sensitivity_problem_ds`` / ``_rand``)
+      Y           [B]     the metric (``metric``: ``config.Y_METRIC`` unless given)
+      dY          [B, P]  d Y / d theta_p
+      elasticity  [B, P]  theta_p dY_p / Y, 0 where Y == 0
+      scaled      [B, P]  dY_p (ub_p - lb_p) with the bounds of ``compute_bound(theta_p, perturbation)``: what a Morris ``mu`` tends to when
+                          the response is linear over the box
+      status      [B]     the solver's flags
+
+    randmod takes theta itself here, not its logarithm (the fits of randmod run in log space): the log-space chain rule is
+    d Y / d log theta_p = dY_p theta_p, which is exactly ``elasticity * Y``."""
+    from .. import batch
+    model = config.ODE_MODEL if model is None else model
+    metric = config.Y_METRIC if metric is None else metric
+    th = np.atleast_2d(np.asarray(theta, dtype=float))
+    define = define_sensitivity_problem_rand if model == 'randmod' else define_sensitivity_problem_ds
+    names = define(num_psites, list(th[0]))['names']
+    width = np.array([[ub - lb for lb, ub in (compute_bound(v, perturbation) for v in row)] for row in th])
+    res = batch.solve_ode_sens_metric_batch(model, th, init_cond, num_psites, time_points, metric=metric, **solver_kw)
+    Y = np.asarray(res.metric.cpu().numpy(), dtype=float)
+    dY = np.asarray(res.dmetric.cpu().numpy(), dtype=float)
+    zero = (Y == 0.0)[:, None]
+    elasticity = np.where(zero, 0.0, th * dY / np.where(zero, 1.0, Y[:, None]))
+    return {"names": names, "Y": Y, "dY": dY, "elasticity": elasticity, "scaled": dY * width, "status": res.status.cpu().numpy()}
 
 
 def _perturb_solve(i_X_tuple):
