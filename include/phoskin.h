@@ -112,8 +112,8 @@ enum {
 typedef struct pk_ctx pk_ctx;
 
 int         pk_version(void);
-/* One context per GPU / per thread.  Owns a HIP stream, two grow-only HBM arenas (staging of the `_host` entry points; per-replica
- * scratch of the largest random-model systems) and a page-locked host buffer for small `_host` calls -- no hipMalloc / hipFree per call. */
+/* One context per GPU / per thread.  Owns a HIP stream, grow-only HBM arenas (staging of the `_host` entry points; per-replica
+ * scratch of the largest random-model systems; the state of pk_fit_protein_rows_batch) and a page-locked host buffer for small `_host` calls -- no hipMalloc / hipFree per call. */
 pk_ctx*     pk_create(int device_id);          /* NULL on failure: reason in pk_create_error() */
 const char* pk_create_error(void);          /* thread-local; empty string after a successful pk_create */
 void        pk_destroy(pk_ctx*);
@@ -198,6 +198,44 @@ int pk_solve_protein_sens_metric_batch(pk_ctx*, int model, int n_sites, int64_t 
                                        const double* t, int T, const pk_solver_opts* opts, int metric_id,
                                        double* metric, double* dmetric, double* flat, double* dflat,
                                        int32_t* status, int32_t* n_steps);
+
+/* The bounded least-squares fit itself, for R independent rows in lockstep -- the numerical core of paramest.normest's
+ * _curve_fit_multistart / find_best_lambda / bootstrap loop (paramest/normest.py:167-326, one scipy.optimize.curve_fit per start there), as
+ * phoskintime_amd.paramest.fit_rows_batch runs it with jacobian="sens": row k fits [flat(theta_k) ; lam_k / P * p_k^2] to [target_k ; 0] with
+ * weights 1 / sigma_k inside the box [lb, ub] from the start point clip(P0_k), by Levenberg-Marquardt with Marquardt scaling, projection on
+ * the box and gain-ratio damping (mu0 = 1e-3; up to 12 damping values mu, 4 mu, 16 mu ... per iteration, trial_levels of them per launch,
+ * the first acceptable one taken).  p is the fitted space: theta = exp(p) under log_space (randmod in the reference), else theta = p.
+ *   P0, p [R,P]; y0 [S] | [R,S]; t [T]; target [F] | [R,F]; sigma NULL (= 1) | [Nr] | [R,Nr] with Nr = F + (use_reg ? P : 0); lam [R], or NULL
+ *   without use_reg; lb, ub [P] | [R,P]; cost [R] = 0.5 |r|^2; r [R,Nr] | NULL the final weighted residuals; JTJ [R,P,P] | NULL, J^T J of the
+ *   weighted residuals at each row's last Jacobian evaluation (what a covariance needs); reason [R] | NULL why the row stopped: 0 ftol / xtol,
+ *   1 gradient / empty free set, 2 damping budget, 3 max_iter.  All of these are DEVICE pointers; counters is a HOST array:
+ *   {iterations, solves, launches, host waits, Jacobian phases, trial rounds}.
+ * Every iteration is a Jacobian phase (gather, pk_solve_protein_sens_batch on the active rows, normal equations: 3 launches, in row chunks
+ * where the Jacobians of a launch would pass 1 GiB) and trial rounds (damped steps, pk_solve_protein_batch on levels x pending rows, accept
+ * rule: 3 launches); the host waits once per phase and once per round, for one flag per row, and nothing else crosses PCIe but the row
+ * lists.  `launches` counts those and the one solve launch of the initial residuals.  State and scratch live in a grow-only arena of the context
+ * that only this entry point uses (no allocation per iteration; pk_workspace_stats does not count it); the call holds the context's lock and returns after its last wait.
+ * A failed solve is very bad, not fatal: its residuals count 1e6 each and its Jacobian entries 0.
+ * Batch independence: all row algebra (csrc/pk_lm.hpp) has one code path and sums in a fixed order, so p, cost, r and JTJ of a row do not
+ * depend on the rows around it, their order, or trial_levels -- PROVIDED the solves do not: opts->kernel = PK_KERNEL_AUTO lets a small system
+ * change kernel family with the batch size (see pk_solver_opts.kernel); a caller who needs the bits pins PK_KERNEL_GROUP or PK_KERNEL_TPR.
+ * opts (NULL = defaults) goes to every solve.  PK_ERR_UNSUPPORTED exactly where pk_solve_protein_sens_batch answers it (sizes without a
+ * sensitivity kernel: difference pk_solve_protein_batch there, as phoskintime_amd.paramest.fit_rows_batch does; a method other than LRP12);
+ * PK_ERR_ARG for a null required pointer, R < 0, T < 1, trial_levels outside 0..12, max_iter < 0; R = 0 is PK_OK. */
+typedef struct pk_fit_opts {
+  int32_t max_iter;      /* iterations (Jacobian evaluations) per row; default 100                                  */
+  int32_t trial_levels;  /* damping values per trial launch; 0 = auto: 3 while <= 256 rows pend, else 1             */
+  int32_t log_space;     /* theta = exp(p)                                                                          */
+  int32_t use_reg;       /* the P ridge rows (lam / P) p^2 are part of the residual                                 */
+  double  ftol, xtol;    /* an accepted step ends the row when dcost <= ftol cost or |dp| <= xtol (xtol + |p|); 1e-10 */
+} pk_fit_opts;
+void pk_default_fit_opts(pk_fit_opts*);
+int  pk_fit_protein_rows_batch(pk_ctx*, int model, int n_sites, int64_t R,
+                               const double* P0, const double* y0, int y0_is_batched, const double* t, int T,
+                               const double* target, int target_is_batched, const double* sigma, int sigma_is_batched,
+                               const double* lam, const double* lb, const double* ub, int bounds_are_batched,
+                               const pk_solver_opts* opts, const pk_fit_opts* fit,
+                               double* p, double* cost, double* r, double* JTJ, int32_t* reason, int64_t counters[6]);
 
 /* Replaces models.{distmod,succmod}.ode_core / models.randmod.ode_system (distmod.py:7-65, succmod.py:9-90,
  * randmod.py:122-247) evaluated for a batch: y [B,S] -> dydt [B,S]. */

@@ -59,11 +59,17 @@ class SolverOpts(C.Structure):
                 ("normalize", C.c_int32), ("stage_form", C.c_int32), ("kernel", C.c_int32), ("err_norm", C.c_int32)]
 
 
+class FitOpts(C.Structure):
+    """Mirror of ``pk_fit_opts`` (include/phoskin.h)."""
+    _fields_ = [("max_iter", C.c_int32), ("trial_levels", C.c_int32), ("log_space", C.c_int32), ("use_reg", C.c_int32),
+                ("ftol", C.c_double), ("xtol", C.c_double)]
+
+
 #: every symbol include/phoskin.h declares (tests/test_capi_symbols.py checks the header against this list)
 SYMBOLS = (
     "pk_version", "pk_create", "pk_create_error", "pk_destroy", "pk_last_error", "pk_set_stream", "pk_use_own_stream", "pk_synchronize", "pk_default_opts", "pk_workspace_stats",
     "pk_protein_n_states", "pk_protein_n_params", "pk_protein_flat_len",
-    "pk_solve_protein_batch", "pk_solve_protein_sens_batch", "pk_solve_protein_sens_metric_batch", "pk_protein_sens_available", "pk_rhs_protein_batch", "pk_jacobian_protein_batch", "pk_steady_state_protein_batch", "pk_morris_build_batch", "pk_morris_effects_batch", "pk_score_fit_batch",
+    "pk_solve_protein_batch", "pk_solve_protein_sens_batch", "pk_solve_protein_sens_metric_batch", "pk_protein_sens_available", "pk_default_fit_opts", "pk_fit_protein_rows_batch", "pk_rhs_protein_batch", "pk_jacobian_protein_batch", "pk_steady_state_protein_batch", "pk_morris_build_batch", "pk_morris_effects_batch", "pk_score_fit_batch",
     "pk_solve_protein_batch_host", "pk_solve_protein_sens_batch_host", "pk_rhs_protein_batch_host", "pk_jacobian_protein_batch_host",
     "pk_dist_sched_parse", "pk_dist_sched_names", "pk_dist_trace_set",
     "pk_time_solve_protein_batch", "pk_measure_hbm_gbs", "pk_measure_hbm_stream_gbs", "pk_measure_fp64_fma_tflops",
@@ -119,6 +125,10 @@ def load():
         getattr(lib, f).restype = i32; getattr(lib, f).argtypes = [vp, i32, i32, i64, vp, vp, i32, vp, i32, optp, vp, vp, vp, vp]
     lib.pk_solve_protein_sens_metric_batch.restype = i32
     lib.pk_solve_protein_sens_metric_batch.argtypes = [vp, i32, i32, i64, vp, vp, i32, vp, i32, optp, i32, vp, vp, vp, vp, vp, vp]
+    lib.pk_default_fit_opts.restype = None; lib.pk_default_fit_opts.argtypes = [C.POINTER(FitOpts)]
+    lib.pk_fit_protein_rows_batch.restype = i32
+    lib.pk_fit_protein_rows_batch.argtypes = [vp, i32, i32, i64, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, optp, C.POINTER(FitOpts),
+                                              vp, vp, vp, vp, vp, C.POINTER(C.c_int64 * 6)]
     solve_args = [vp, i32, i32, i64, vp, vp, i32, vp, i32, optp, vp, vp, vp, i32, vp, vp]
     for f in ("pk_solve_protein_batch", "pk_solve_protein_batch_host"):
         getattr(lib, f).restype = i32; getattr(lib, f).argtypes = solve_args
@@ -188,6 +198,18 @@ def default_opts(**kw) -> SolverOpts:
             v = NORMS[v]
         if not hasattr(o, k):
             raise TypeError(f"unknown solver option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def default_fit_opts(**kw) -> FitOpts:
+    o = FitOpts()
+    load().pk_default_fit_opts(C.byref(o))
+    for k, v in kw.items():
+        if v is None:
+            continue
+        if not hasattr(o, k):
+            raise TypeError(f"unknown fit option {k!r}")
         setattr(o, k, v)
     return o
 

@@ -272,6 +272,101 @@ def solve_ode_sens_metric_batch(model, theta: ArrayLike, init_cond: ArrayLike, n
     return out
 
 
+@dataclass
+class NativeFit:
+    """Outputs of ``fit_rows_native`` (tensors live on the GPU)."""
+    p: torch.Tensor                   # [R, P]     final parameters (fitted space)
+    cost: torch.Tensor                # [R]        0.5 |r|^2
+    r: torch.Tensor                   # [R, Nr]    final weighted residuals
+    JTJ: torch.Tensor                 # [R, P, P]  J^T J at each row's last Jacobian evaluation
+    reason: torch.Tensor              # [R] int32  0 ftol / xtol | 1 gradient / free set | 2 damping budget | 3 max_iter
+    counters: dict                    # iterations, solves, launches, host_waits, jacobian_phases, trial_rounds
+
+
+FIT_COUNTERS = ("iterations", "solves", "launches", "host_waits", "jacobian_phases", "trial_rounds")
+
+
+def fit_rows_native(model, P0: ArrayLike, init_cond: ArrayLike, num_psites: int, t: ArrayLike, target: ArrayLike, *, sigma: Optional[ArrayLike] = None,
+                    lam: Optional[ArrayLike] = None, bounds=None, log_space: bool = False, use_reg: Optional[bool] = None, max_iter: int = 100,
+                    ftol: float = 1e-10, xtol: float = 1e-10, trial_levels: int = 0, method: Union[str, int, None] = None,
+                    rtol: Optional[float] = None, atol: Optional[float] = None, h0: Optional[float] = None, max_steps: Optional[int] = None,
+                    clip_nonneg: bool = True, normalize: bool = False, kernel: Union[str, int, None] = None, device: Optional[int] = None) -> NativeFit:
+    """R bounded least-squares fits in lockstep with the whole Levenberg-Marquardt state in HBM (pk_fit_protein_rows_batch, include/phoskin.h):
+    row k fits ``[flat(theta_k) ; lam_k / P * p_k**2]`` to ``[target_k ; 0]`` with weights ``1 / sigma_k`` inside ``bounds`` from ``P0[k]``.
+    P0 [R, P] (fitted space: theta = exp(p) under ``log_space``); init_cond [S] or [R, S]; target [F] or [R, F]; sigma None, [Nr] or [R, Nr];
+    lam None, scalar or [R]; bounds (lb, ub), each [P] or [R, P].  ``use_reg`` None: ridge rows iff any lam > 0.  A row's result does not depend
+    on the rows around it when ``kernel`` pins a family ("group" / "tpr").  Synchronous.  Raises ``PhoskinError`` (PK_ERR_UNSUPPORTED) for
+    sizes without a sensitivity kernel (``sens_available``) and for a method other than LRP12."""
+    ctx = get_context(device)
+    dev = torch.device("cuda", ctx.device)
+    mid = model_id(model)
+    n = int(num_psites)
+    P0d = _dev_f64(P0, dev)
+    if P0d.dim() == 1:
+        P0d = P0d.unsqueeze(0)
+    if bounds is None:
+        raise ValueError("bounds = (lb, ub) is required")
+    tt = _dev_f64(np.atleast_1d(t) if not isinstance(t, torch.Tensor) else t, dev).reshape(-1)
+    T = tt.numel()
+    if T < 1:
+        raise ValueError("t must hold at least one time point")
+    R = P0d.shape[0]
+    lamd = None
+    if lam is not None:
+        lamd = _dev_f64(lam, dev)
+        lamd = lamd.expand(R).contiguous() if lamd.dim() == 0 else lamd
+        if lamd.shape != (R,):
+            raise ValueError(f"lam must be a scalar or [{R}], got {tuple(lamd.shape)}")
+    if use_reg is None:
+        use_reg = bool(lamd is not None and R > 0 and bool((lamd > 0.0).any()))
+    if use_reg and lamd is None:
+        raise ValueError("use_reg needs lam")
+    opts = default_opts(method=method, rtol=rtol, atol=atol, h0=h0, max_steps=max_steps, clip_nonneg=int(bool(clip_nonneg)),
+                        normalize=int(bool(normalize)), kernel=kernel)
+    fopts = _capi.default_fit_opts(max_iter=int(max_iter), trial_levels=int(trial_levels), log_space=int(bool(log_space)), use_reg=int(bool(use_reg)),
+                                   ftol=float(ftol), xtol=float(xtol))
+    known = mid in (DIST, SUCC, RAND) and n >= 1 and (mid != RAND or n <= 20)
+    if known:
+        S, P, F = n_states(mid, n), n_params(mid, n), flat_len(mid, n, T)
+        if P0d.dim() != 2 or P0d.shape[1] != P:
+            raise ValueError(f"P0 must be [R, {P}] for model {mid} with {n} sites, got {tuple(P0d.shape)}")
+    else:                             # the entry point names what is wrong with (model, n_sites)
+        S, P, F = 1, P0d.shape[1], 1
+    Nr = F + (P if use_reg else 0)
+
+    def rows_or_shared(x, width, name):
+        x = _dev_f64(x, dev)
+        if x.shape == (width,):
+            return x, 0
+        if x.shape == (R, width):
+            return x, 1
+        raise ValueError(f"{name} must be [{width}] or [{R}, {width}], got {tuple(x.shape)}")
+
+    cnt = (C.c_int64 * 6)()
+    out = NativeFit(p=torch.empty((R, P), dtype=torch.float64, device=dev), cost=torch.empty((R,), dtype=torch.float64, device=dev),
+                    r=torch.empty((R, Nr), dtype=torch.float64, device=dev), JTJ=torch.zeros((R, P, P), dtype=torch.float64, device=dev),
+                    reason=torch.zeros((R,), dtype=torch.int32, device=dev), counters={})
+    if known:
+        y0, y0b = rows_or_shared(init_cond, S, "init_cond")
+        tg, tgb = rows_or_shared(target, F, "target")
+        sg, sgb = (None, 0) if sigma is None else rows_or_shared(sigma, Nr, "sigma")
+        lb, lbb = rows_or_shared(bounds[0], P, "lb")
+        ub, ubb = rows_or_shared(bounds[1], P, "ub")
+        if lbb != ubb:                # one flag covers both bounds
+            lb, ub = (b if bb else b.expand(R, P).contiguous() for b, bb in ((lb, lbb), (ub, ubb)))
+            lbb = 1
+    else:
+        y0 = tg = lb = ub = P0d
+        sg, y0b, tgb, sgb, lbb = None, 0, 0, 0, 0
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.check(ctx.lib.pk_fit_protein_rows_batch(ctx.handle, mid, n, R, _ptr(P0d), _ptr(y0), y0b, _ptr(tt), T, _ptr(tg), tgb, _ptr(sg), sgb, _ptr(lamd),
+                                                _ptr(lb), _ptr(ub), lbb, C.byref(opts), C.byref(fopts), _ptr(out.p), _ptr(out.cost), _ptr(out.r),
+                                                _ptr(out.JTJ), _ptr(out.reason), C.byref(cnt)))
+    ctx.synchronize()
+    out.counters = dict(zip(FIT_COUNTERS, (int(v) for v in cnt)))
+    return out
+
+
 def rhs_batch(model, theta: ArrayLike, y: ArrayLike, num_psites: int, device: Optional[int] = None) -> torch.Tensor:
     """dy/dt for B (theta, y) pairs: reference ``ode_core`` / ``ode_system`` batched.  Returns [B, S] on the GPU."""
     ctx = get_context(device)

@@ -25,6 +25,8 @@ struct pk_ctx {
   std::string err;
   hipEvent_t ev0, ev1;
   pk_arena stage, scratch;                       // device memory
+  pk_arena fit;                                  // state and scratch of pk_fit_protein_rows_batch (pk_lm.hip): its own, so that a fit neither moves
+  void* fit_pin = nullptr; size_t fit_pin_bytes = 0;      // the `_host` staging nor shows in its counters (pk_workspace_stats); page-locked row lists / flags
   void* pin = nullptr; size_t pin_bytes = 0; long long pin_allocs = 0;      // page-locked host staging for small calls
   // The header asks for one context per thread, but a shared one must not corrupt memory: every `_host` entry point holds `mu` from
   // staging to the final synchronisation (they share `stage` / `pin`), and launches that use `scratch` are ordered by `scratch_ev`
@@ -208,6 +210,8 @@ void pk_destroy(pk_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   if (c->stage.p) (void)hipFree(c->stage.p);
   if (c->scratch.p) (void)hipFree(c->scratch.p);
+  if (c->fit.p) (void)hipFree(c->fit.p);
+  if (c->fit_pin) (void)hipHostFree(c->fit_pin);
   if (c->pin) (void)hipHostFree(c->pin);
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
@@ -232,6 +236,26 @@ int pk_ctx_scratch_launch(pk_ctx* c, size_t bytes, hipError_t (*launch)(void* sc
   PK_HIP(c, launch(c->scratch.p, c->stream, user));
   PK_HIP(c, hipEventRecord(c->scratch_ev, c->stream));
   c->scratch_used = true;
+  return PK_OK;
+}
+
+// for the fit driver (pk_lm.hip): the context's lock, and the fit's own grow-only device arena and page-locked buffer at the sizes one fit
+// needs (the caller holds the lock from here to its last use of either; no other entry point touches them)
+void pk_ctx_lock(pk_ctx* c) { c->mu.lock(); }
+void pk_ctx_unlock(pk_ctx* c) { c->mu.unlock(); }
+int pk_ctx_fit_reserve(pk_ctx* c, size_t dev_bytes, size_t pin_bytes, void** dev, void** pin) {
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  PK_HIP(c, hipSetDevice(c->device));
+  int rc = arena_reserve(c, c->fit, dev_bytes);
+  if (rc) return rc;
+  if (pin_bytes > c->fit_pin_bytes) {
+    const size_t want = pin_bytes + pin_bytes / 2 + (64u << 10);
+    if (c->fit_pin) { PK_HIP(c, hipDeviceSynchronize()); PK_HIP(c, hipHostFree(c->fit_pin)); c->fit_pin = nullptr; c->fit_pin_bytes = 0; }
+    hipError_t e = hipHostMalloc(&c->fit_pin, want, hipHostMallocDefault);
+    if (e != hipSuccess) { c->fit_pin = nullptr; return fail(c, PK_ERR_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
+    c->fit_pin_bytes = want;
+  }
+  *dev = c->fit.p; *pin = c->fit_pin;
   return PK_OK;
 }
 

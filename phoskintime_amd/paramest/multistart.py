@@ -66,12 +66,14 @@ class RowsFit:
     JTJ: np.ndarray             # [R, P, P] J^T J of the weighted residuals at the last Jacobian evaluation (what pcov needs)
     n_iter: int
     n_solves: int
-    n_launches: int = 0         # solve launches (Jacobian batches + trial batches)
+    n_launches: int = 0         # solve launches (Jacobian batches + trial batches); driver="native": every launch of the loop
+    counters: Optional[dict] = None          # driver="native": the six counters of pk_fit_protein_rows_batch
+    reason: Optional[np.ndarray] = None      # driver="native": [R] 0 ftol / xtol, 1 gradient / free set, 2 damping budget, 3 max_iter
 
 
 def fit_rows_batch(model: str, num_psites: int, time_points, P0, init_cond, target, sigma=None, lam=0.0, bounds=None,
                    max_iter: int = 100, ftol: float = 1e-10, xtol: float = 1e-10, device_algebra="auto", jacobian="auto", trial_levels="auto",
-                   force_reg: Optional[bool] = None, lm_algebra="auto", **solver_kw) -> RowsFit:
+                   force_reg: Optional[bool] = None, lm_algebra="auto", driver: str = "python", **solver_kw) -> RowsFit:
     """R independent bounded least-squares problems in lockstep: row k fits ``[flat(p) ; lam_k / P * p**2]`` to ``[target_k ; 0]`` with
     weights ``sigma_k`` from the start point ``P0[k]``.  Rows may be the starts of one multistart fit, the (lambda, weight) grid of
     ``find_best_lambda``, bootstrap replicates, different proteins of the same size -- or any mix.
@@ -102,7 +104,25 @@ def fit_rows_batch(model: str, num_psites: int, time_points, P0, init_cond, targ
     and the predicted reductions are device ops, and only vectors (gradient, diagonal, trial points' costs: O(P) per row) cross PCIe.
     "auto": device in every iteration whose ACTIVE rows x P^2 >= 2^19 (and the residual algebra is on the device), else host -- small
     problems, and the late iterations of big ones, are launch-bound: a dozen tiny device ops per round cost more than numpy on
-    48 x 12 x 12 numbers (measured: 480 rows at P = 20, 60 iterations: 351 ms all-device, 261 ms all-host)."""
+    48 x 12 x 12 numbers (measured: 480 rows at P = 20, 60 iterations: 351 ms all-device, 261 ms all-host).
+
+    ``driver``: "python" (default) is this function's own host loop, described above.  "native" hands the whole fit to the library's
+    ``pk_fit_protein_rows_batch`` (include/phoskin.h; ``batch.fit_rows_native``): the same rules with the sensitivity Jacobian, the
+    Levenberg-Marquardt state in HBM, the row algebra in small kernels with one code path and a fixed summation order, and one host wait per
+    Jacobian phase and per trial round.  ``n_launches`` then counts every launch of the loop (three per phase and per round, and the initial
+    solve), ``n_iter`` the iterations that ran (the Python loop also counts the pass that finds no active row), ``counters`` holds the entry
+    point's six counters and ``reason`` why each row stopped.  It takes ``jacobian`` "auto" / "sens"
+    only and no ``lm_algebra`` / ``device_algebra`` choice (``ValueError`` for "fd" or a non-default ``lm_algebra``), and raises
+    ``PhoskinError`` where no sensitivity kernel exists."""
+    if driver not in ("python", "native"):
+        raise ValueError("driver must be 'python' or 'native'")
+    if driver == "native":
+        if jacobian not in ("auto", "sens"):
+            raise ValueError("driver='native' takes the sensitivity Jacobian only (jacobian='auto' or 'sens')")
+        if lm_algebra != "auto":
+            raise ValueError("driver='native' has one row algebra: lm_algebra must stay 'auto'")
+        return _fit_rows_native(model, num_psites, time_points, P0, init_cond, target, sigma, lam, bounds, max_iter, ftol, xtol, trial_levels,
+                                force_reg, solver_kw)
     import torch
     log_space = (model == "randmod")
     P0 = np.atleast_2d(np.asarray(P0, float))
@@ -364,10 +384,36 @@ def fit_rows_batch(model: str, num_psites: int, time_points, P0, init_cond, targ
     return RowsFit(p=p, cost=cost, r=r_out, JTJ=JTJ, n_iter=it, n_solves=n_solves, n_launches=n_launches)
 
 
+def _fit_rows_native(model, num_psites, time_points, P0, init_cond, target, sigma, lam, bounds, max_iter, ftol, xtol, trial_levels, force_reg,
+                     solver_kw) -> RowsFit:
+    """``fit_rows_batch(driver="native")``: the arguments of the Python driver mapped onto ``batch.fit_rows_native``."""
+    P0 = np.atleast_2d(np.asarray(P0, float))
+    R, P = P0.shape
+    lam = np.broadcast_to(np.asarray(lam, float), (R,)).copy()
+    use_reg = bool(np.any(lam > 0.0)) if force_reg is None else bool(force_reg)
+    native_opts = ("method", "rtol", "atol", "h0", "max_steps", "clip_nonneg", "normalize", "kernel")
+    extra = sorted(k for k, v in solver_kw.items() if v is not None and k not in native_opts)
+    if extra:
+        raise ValueError(f"driver='native' takes the solver options {native_opts}, not {extra}")
+    if bounds is None:
+        raise ValueError("bounds = (lb, ub) is required")
+    fit = batch.fit_rows_native(model, P0, init_cond, num_psites, time_points, target, sigma=sigma, lam=lam, bounds=bounds,
+                                log_space=(model == "randmod"), use_reg=use_reg, max_iter=max_iter, ftol=ftol, xtol=xtol,
+                                trial_levels=0 if trial_levels == "auto" else int(trial_levels),
+                                **{k: v for k, v in solver_kw.items() if v is not None})
+    c = fit.counters
+    return RowsFit(p=fit.p.cpu().numpy(), cost=fit.cost.cpu().numpy(), r=fit.r.cpu().numpy(), JTJ=fit.JTJ.cpu().numpy(), n_iter=c["iterations"],
+                   n_solves=c["solves"], n_launches=c["launches"], counters=c, reason=fit.reason.cpu().numpy())
+
+
 def fit_rows_sharded(model: str, num_psites: int, time_points, P0, init_cond, target, sigma=None, lam=0.0, bounds=None, **kw) -> RowsFit:
     """``fit_rows_batch`` with the R problems dealt round-robin over the ranks of an initialised ``torch.distributed`` group (one process
     per GPU): every rank fits its rows, then ONE all-gather of the per-row results [p | cost | J^T J] (P + 1 + P^2 doubles per row) gives
-    every rank the complete ``RowsFit``.  Rows never interact, so the result equals the single-GPU fit row for row.  Without a process
+    every rank the complete ``RowsFit``.  Rows never interact, but "equal to the single-GPU fit row for row" holds bit for bit only where a
+    row's arithmetic does not depend on the batch around it: with ``driver="native"`` and a pinned kernel family (``kernel="group"`` or
+    ``"tpr"``) it does by construction (one code path, fixed summation order); with the Python driver it holds within ONE ``lm_algebra``
+    choice ("host" or "device" -- "auto" re-decides from the number of active rows, which differs between a shard and the whole) and a
+    pinned kernel family, and then to the rounding of batched LU codes that may block by batch size.  Without a process
     group (or at world size 1) it is ``fit_rows_batch``.  ``n_iter`` / ``n_solves`` / ``n_launches`` of the result are RANK-LOCAL counters
     (the work this rank did), not totals."""
     import torch
@@ -422,13 +468,13 @@ def _scores(model, theta_space_p, init_cond, num_psites, time_points, target, so
 def curve_fit_multistart_batch(model: str, init_cond, num_psites: int, time_points, target, base_p0, bounds: Tuple, sigma=None,
                                lam: float = 0.0, gene: str = "", n_starts: int = 24, jitter_frac: float = 0.10, seed: int = 42,
                                max_iter: int = 100, ftol: float = 1e-10, xtol: float = 1e-10, absolute_sigma: bool = True,
-                               **solver_kw) -> FitResult:
+                               driver: str = "python", **solver_kw) -> FitResult:
     """Fit ``flat(p)`` to ``target`` (+ ridge term ``lam``) from ``n_starts`` start points at once.  ``bounds = (lb, ub)`` in the fitted
     space; ``sigma`` covers the data block and, when ``lam > 0``, the P regularisation rows as well (as in the reference)."""
     lb, ub = (np.asarray(b, float) for b in bounds)
     P0 = multistart_candidates(gene, base_p0, lb, ub, n_starts, jitter_frac, seed)
     fit = fit_rows_batch(model, num_psites, time_points, P0, init_cond, target, sigma=sigma, lam=lam, bounds=(lb, ub), max_iter=max_iter,
-                         ftol=ftol, xtol=xtol, **solver_kw)
+                         ftol=ftol, xtol=xtol, driver=driver, **solver_kw)
     # score every start like the reference (solve at popt, score_fit against the un-regularised target) and keep the best
     scores = _scores(model, fit.p, init_cond, num_psites, time_points, target, solver_kw)
     best = int(np.argmin(scores))
@@ -437,7 +483,7 @@ def curve_fit_multistart_batch(model: str, init_cond, num_psites: int, time_poin
 
 
 def find_best_lambda_batch(model: str, target, p0, time_points, free_bounds: Tuple, init_cond, num_psites: int, weight_options: dict,
-                           lambdas=None, max_iter: int = 100, **solver_kw):
+                           lambdas=None, max_iter: int = 100, driver: str = "python", **solver_kw):
     """``paramest.normest.find_best_lambda`` + ``worker_find_lambda`` (normest.py:36-166): for every lambda in ``lambdas`` (default
     ``np.logspace(-2, 0, 10)``) and every weighting ``sigma`` in ``weight_options`` (``models.weights.get_weight_options`` with
     ``use_regularization=True``: Nd + P entries each) one fit from ``p0``; the reference runs these 10 x W ``curve_fit`` calls in a
@@ -451,7 +497,7 @@ def find_best_lambda_batch(model: str, target, p0, time_points, free_bounds: Tup
     L, W, P = lambdas.size, len(keys), p0.size
     sig = np.stack([np.asarray(weight_options[k], float) for k in keys])               # [W, Nd + P]
     fit = fit_rows_batch(model, num_psites, time_points, np.tile(p0, (L * W, 1)), init_cond, target, sigma=np.tile(sig, (L, 1)),
-                         lam=np.repeat(lambdas, W), bounds=free_bounds, max_iter=max_iter, **solver_kw)
+                         lam=np.repeat(lambdas, W), bounds=free_bounds, max_iter=max_iter, driver=driver, **solver_kw)
     scores = _scores(model, fit.p, init_cond, num_psites, time_points, target, solver_kw).reshape(L, W)
     # the reference keeps the first strict improvement while scanning weights inside a lambda, then lambdas: same tie-breaking
     best_per_lam = np.argmin(scores, axis=1)
@@ -461,7 +507,7 @@ def find_best_lambda_batch(model: str, target, p0, time_points, free_bounds: Tup
 
 def bootstrap_fit_batch(model: str, target_fit, popt, time_points, free_bounds: Tuple, init_cond, num_psites: int, sigma=None,
                         lam: float = 0.0, bootstraps: int = 10, noise: float = 0.05, rng=None, absolute_sigma: bool = True,
-                        max_iter: int = 100, **solver_kw):
+                        max_iter: int = 100, driver: str = "python", **solver_kw):
     """The bootstrap loop of ``normest`` (normest.py:488-523): ``bootstraps`` refits from ``popt`` of ``target_fit * (1 + N(0, noise))``
     (noise on the regularisation zeros is a no-op, as in the reference), all replicates in one lockstep batch.
     Returns (mean of the replicate estimates, mean of their covariances or None, all estimates [bootstraps, P])."""
@@ -472,7 +518,7 @@ def bootstrap_fit_batch(model: str, target_fit, popt, time_points, free_bounds: 
     noisy = np.stack([tf * (1 + rng.normal(0, noise, size=tf.shape)) for _ in range(bootstraps)])
     Nd = tf.size - (P if lam > 0.0 else 0)
     fit = fit_rows_batch(model, num_psites, time_points, np.tile(popt, (bootstraps, 1)), init_cond, noisy[:, :Nd], sigma=sigma, lam=lam,
-                         bounds=free_bounds, max_iter=max_iter, **solver_kw)
+                         bounds=free_bounds, max_iter=max_iter, driver=driver, **solver_kw)
     covs = [c for c in (_pcov(fit.JTJ[k], fit.cost[k], absolute_sigma, fit.r.shape[1]) for k in range(bootstraps)) if c is not None]
     return fit.p.mean(axis=0), (np.mean(covs, axis=0) if covs else None), fit.p
 
