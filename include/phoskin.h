@@ -199,6 +199,36 @@ int pk_solve_protein_sens_metric_batch(pk_ctx*, int model, int n_sites, int64_t 
                                        double* metric, double* dmetric, double* flat, double* dflat,
                                        int32_t* status, int32_t* n_steps);
 
+/* A weighted sum over the entries of flat AND its gradient from ONE integration: the VJP flavour of the output stage of the kernels behind
+ * pk_solve_protein_sens_batch.  It is the vector-Jacobian product w^T d flat / d theta a backward pass needs, and the weighted least-squares
+ * cost with its gradient J^T r that an optimiser other than Levenberg-Marquardt takes -- without dflat [B,F,P] in memory.
+ *   w [F] | [B,F]; target NULL | [F] | [B,F]; value [B]; grad [B,P]; flat [B,F] | NULL (NULL = not written: B (1 + P) doubles leave the
+ *   kernel instead of B F (1 + P)); status / n_steps as above.  All arrays are device pointers; the call is asynchronous on the context's stream.
+ * With v[f] the post-processed value of flat entry f (clipped at 0 under opts->clip_nonneg, scaled by 1 / y0 under opts->normalize: exactly as
+ * flat stores it) and d[f,p] its post-processed derivative (scaled alike; 0 where the state is below -atol under clip_nonneg, the rule of
+ * dflat; 0 at output time 0, the initial values being data):
+ *   linear mode        (target == NULL)   c[f] = w[f]                                   value = sum_f w[f] v[f]
+ *   least-squares mode (target != NULL)   r[f] = w[f] (v[f] - target[f]),  c[f] = w[f] r[f]   value = 1/2 sum_f r[f]^2     (w = 1 / sigma)
+ *   both                                  grad[p] = sum_f c[f] d[f,p]
+ * Least-squares mode is the cost and J^T r of the data rows of pk_fit_protein_rows_batch's residual.  The sum index is the FLAT index: the
+ * mRNA row at the first five output times has no slot in flat and contributes nothing (the opposite of the metric flavour, which sums it);
+ * with T <= 5 the mRNA block is empty.  Every column keeps one running sum over its entries in output order, stored once; no atomics, no
+ * order that depends on the batch.
+ * Failure follows dflat's NaN fill, the NaN entries entering the sums: a flagged replica has value = NaN, and NaN in the columns of grad whose
+ * chunk was flagged (kernels that cut the columns into chunks: chunk 0 forms value and flat, every chunk integrates the state itself and
+ * forms its own columns -- in least-squares mode with c[f] from its own state values, which differ from flat's within rtol / atol; status
+ * is the OR over the chunks).  T = 1: value is that of the post-processed y0, grad is 0.
+ * Same sizes (pk_protein_sens_available), options (LRP12 only) and kernel per size, PK_SENS_ROWS included, as pk_solve_protein_sens_batch,
+ * and PK_ERR_UNSUPPORTED in the same cases; PK_ERR_ARG for a null w, value or grad; B = 0 is PK_OK.
+ * flat, status and n_steps are bit-equal to those of pk_solve_protein_sens_batch for the same inputs; value and grad do not depend on
+ * whether flat was asked for, nor on the batch around a replica. */
+int pk_solve_protein_sens_vjp_batch(pk_ctx*, int model, int n_sites, int64_t B,
+                                    const double* theta, const double* y0, int y0_is_batched,
+                                    const double* t, int T, const pk_solver_opts* opts,
+                                    const double* w, int w_is_batched, const double* target, int target_is_batched,
+                                    double* value, double* grad, double* flat,
+                                    int32_t* status, int32_t* n_steps);
+
 /* The bounded least-squares fit itself, for R independent rows in lockstep -- the numerical core of paramest.normest's
  * _curve_fit_multistart / find_best_lambda / bootstrap loop (paramest/normest.py:167-326, one scipy.optimize.curve_fit per start there), as
  * phoskintime_amd.paramest.fit_rows_batch runs it with jacobian="sens": row k fits [flat(theta_k) ; lam_k / P * p_k^2] to [target_k ; 0] with

@@ -273,6 +273,74 @@ def solve_ode_sens_metric_batch(model, theta: ArrayLike, init_cond: ArrayLike, n
 
 
 @dataclass
+class SensVjpResult:
+    """Outputs of ``solve_ode_vjp_batch`` (tensors live on the GPU; ``None`` where not requested)."""
+    value: torch.Tensor               # [B]        sum_f w_f flat_f, or 0.5 |w (flat - target)|^2
+    grad: torch.Tensor                # [B, P]     d value / d theta
+    flat: Optional[torch.Tensor]      # [B, F]
+    status: torch.Tensor              # [B] int32
+    n_steps: torch.Tensor             # [B, 2] int32
+
+
+def solve_ode_vjp_batch(model, theta: ArrayLike, init_cond: ArrayLike, num_psites: int, t: ArrayLike, w: ArrayLike,
+                        target: Optional[ArrayLike] = None, want_flat: bool = False, *,
+                        rtol: Optional[float] = None, atol: Optional[float] = None, h0: Optional[float] = None,
+                        max_steps: Optional[int] = None, clip_nonneg: bool = True, normalize: bool = False,
+                        device: Optional[int] = None) -> SensVjpResult:
+    """A weighted sum over ``flat`` AND its gradient for B parameter vectors from one launch: the kernels of ``solve_ode_sens_batch`` with
+    the contraction over the flat index formed in their output stage, so that ``dflat`` never exists (include/phoskin.h,
+    pk_solve_protein_sens_vjp_batch, has the formulas and the clip / normalise / NaN rules).  ``w``: [F] or [B, F].  Without ``target``:
+    ``value = sum_f w_f flat_f`` and ``grad = w^T dflat`` (the vector-Jacobian product of a backward pass).  With ``target`` ([F] or
+    [B, F]) and ``w = 1 / sigma``: ``value = 0.5 |w (flat - target)|^2`` and ``grad = J^T r``.  ``flat`` is written only on request and is
+    then bit-equal to ``solve_ode_sens_batch``'s.  Same sizes as ``solve_ode_sens_batch`` (``sens_available``); raises ``PhoskinError``
+    (PK_ERR_UNSUPPORTED) beyond."""
+    ctx = get_context(device)
+    dev = torch.device("cuda", ctx.device)
+    mid = model_id(model)
+    n = int(num_psites)
+    S, P = n_states(mid, n), n_params(mid, n)
+    th = _dev_f64(theta, dev)
+    if th.dim() == 1:
+        th = th.unsqueeze(0)
+    if th.dim() != 2 or th.shape[1] != P:
+        raise ValueError(f"theta must be [B, {P}] for model {mid} with {n} sites, got {tuple(th.shape)}")
+    B = th.shape[0]
+    y0 = _dev_f64(init_cond, dev)
+    if y0.shape == (S,):
+        batched = 0
+    elif y0.shape == (B, S):
+        batched = 1
+    else:
+        raise ValueError(f"init_cond must be [{S}] or [{B}, {S}], got {tuple(y0.shape)}")
+    tt = _dev_f64(np.atleast_1d(t) if not isinstance(t, torch.Tensor) else t, dev).reshape(-1)
+    T = tt.numel()
+    if T < 1:
+        raise ValueError("t must hold at least one time point")
+    F = flat_len(mid, n, T)
+
+    def per_entry(a, name):
+        a = _dev_f64(a, dev)
+        if a.shape == (F,):
+            return a, 0
+        if a.shape == (B, F):
+            return a, 1
+        raise ValueError(f"{name} must be [{F}] or [{B}, {F}], got {tuple(a.shape)}")
+
+    ww, w_batched = per_entry(w, "w")
+    tg, tg_batched = per_entry(target, "target") if target is not None else (None, 0)
+    opts = default_opts(rtol=rtol, atol=atol, h0=h0, max_steps=max_steps, clip_nonneg=int(bool(clip_nonneg)), normalize=int(bool(normalize)))
+    out = SensVjpResult(value=torch.empty((B,), dtype=torch.float64, device=dev), grad=torch.empty((B, P), dtype=torch.float64, device=dev),
+                        flat=torch.empty((B, F), dtype=torch.float64, device=dev) if want_flat else None,
+                        status=torch.zeros((B,), dtype=torch.int32, device=dev), n_steps=torch.zeros((B, 2), dtype=torch.int32, device=dev))
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.check(ctx.lib.pk_solve_protein_sens_vjp_batch(ctx.handle, mid, n, B, _ptr(th), _ptr(y0), batched, _ptr(tt), T, C.byref(opts),
+                                                      _ptr(ww), w_batched, _ptr(tg), tg_batched, _ptr(out.value), _ptr(out.grad), _ptr(out.flat),
+                                                      _ptr(out.status), _ptr(out.n_steps)))
+    out._keepalive = (th, y0, tt, ww, tg)  # type: ignore[attr-defined]
+    return out
+
+
+@dataclass
 class NativeFit:
     """Outputs of ``fit_rows_native`` (tensors live on the GPU)."""
     p: torch.Tensor                   # [R, P]     final parameters (fitted space)

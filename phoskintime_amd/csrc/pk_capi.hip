@@ -498,6 +498,32 @@ int pk_solve_protein_sens_metric_batch(pk_ctx* c, int model, int n_sites, int64_
   return PK_OK;
 }
 
+int pk_solve_protein_sens_vjp_batch(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched,
+                                    const double* t, int T, const pk_solver_opts* opts_in, const double* w, int w_is_batched, const double* target,
+                                    int target_is_batched, double* value, double* grad, double* flat, int32_t* status, int32_t* n_steps) {
+  if (!c) return PK_ERR_ARG;
+  int rc = check_model(c, model, n_sites);
+  if (rc) return rc;
+  if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
+  if (T < 1) return fail(c, PK_ERR_ARG, "T must be >= 1");
+  if (!pk::sens_available(model, n_sites))
+    return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)");
+  if (B == 0) return PK_OK;
+  if (!theta || !y0 || !t || !w || !value || !grad) return fail(c, PK_ERR_ARG, "theta, y0, t, w, value and grad must be non-null");
+  const pk_solver_opts o = solver_opts(opts_in);
+  if (o.method != PK_METHOD_LRP12 || o.stage_form) return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities integrate with method LRP12 (the default) only");
+  if (!(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
+  pk::SensVjpArgs sa;           // the VJP flavour of the output stage: flat may be null, target null selects the linear mode
+  sa.s = solve_args(model, n_sites, B, theta, y0, y0_is_batched, t, T, o, nullptr, flat, nullptr, 0, status, n_steps);
+  sa.w = w; sa.w_batched = w_is_batched ? 1 : 0;
+  sa.target = target; sa.target_batched = (target && target_is_batched) ? 1 : 0;
+  sa.value = value; sa.grad = grad;
+  if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
+  PK_HIP(c, hipSetDevice(c->device));
+  PK_HIP(c, pk::launch_sens_vjp(sa, model, c->stream));
+  return PK_OK;
+}
+
 int pk_solve_protein_batch_host(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0,
                                 int y0_is_batched, const double* t, int T, const pk_solver_opts* opts, double* sol,
                                 double* flat, double* metric, int metric_id, int32_t* status, int32_t* n_steps) {

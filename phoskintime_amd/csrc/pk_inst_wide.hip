@@ -87,6 +87,8 @@ hipError_t launch_rand_sens(const SensArgs& a, hipStream_t st) { return launch_r
 // its metric flavour (pk_sens.hpp, SensMetricArgs).  Here and not beside the other metric instantiations: pk_wide.hpp, which pk_rand_sens.hpp
 // builds on, defines kernels that one translation unit alone may hold
 hipError_t launch_rand_sens_metric(const SensMetricArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
+// and its VJP flavour (SensVjpArgs), here for the same reason
+hipError_t launch_rand_sens_vjp(const SensVjpArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
 
 bool rand_dense_available(int n_sites) {
   static const bool on = [] { const char* v = getenv("PK_WIDE_RAND_DENSE"); return !(v && v[0] == '0'); }();

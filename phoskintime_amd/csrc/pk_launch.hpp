@@ -39,6 +39,9 @@ hipError_t launch_sens(const SensArgs&, int model, hipStream_t);
 // their metric flavour (m = _compute_Y and d m / d theta; flat / dflat optional): the same kernel per size as launch_sens takes
 struct SensMetricArgs;
 hipError_t launch_sens_metric(const SensMetricArgs&, int model, hipStream_t);
+// their VJP flavour (a weighted sum over flat and its gradient; flat optional, no dflat): the same kernel per size again
+struct SensVjpArgs;
+hipError_t launch_sens_vjp(const SensVjpArgs&, int model, hipStream_t);
 // workgroup-per-replica kernels for systems beyond 64 rows (pk_wide.hpp)
 bool wide_chain_fits(int S, int n_sites);                                   // distmod / succmod: 15 LDS vectors of S doubles
 hipError_t launch_wide_chain(const SolveArgs&, int model, hipStream_t);     // LRP12, exact solves

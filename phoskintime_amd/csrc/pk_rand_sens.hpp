@@ -31,10 +31,10 @@ __host__ __device__ constexpr size_t rand_sens_lds_bytes(int n) {
 }
 
 // TBP: side of the thread grid over the even Schur complement: 16 (256 threads) or 8 (n = 6: ONE wave per column chunk, 4 x 4 blocks per lane)
-// Args = SensArgs, or SensMetricArgs (pk_sens.hpp) for the metric flavour of the output stage
+// Args = SensArgs, or SensMetricArgs / SensVjpArgs (pk_sens.hpp) for the metric / VJP flavour of the output stage
 template <int NB, int TBP = 16, class Args = SensArgs>
 __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const Args SA) {
-  constexpr bool MET = sens_metric_flavour<Args>();
+  constexpr bool MET = sens_metric_flavour<Args>(), VJP = sens_vjp_flavour<Args>();
   static_assert((NB == 6 || NB == 7) && (TBP == 16 || TBP == 8) && (1 << NB) <= TBP * TBP, "thread grid over the even Schur complement");
   using Tab = ResolventTab<PK_METHOD_LRP12>;
   constexpr int NALL = 1 << NB, NM = NALL / 2, TB = TBP, TS = NM / TB, NT = TB * TB, KC = kRandSensKC, KT = KC - 1, S = NALL + 1;
@@ -99,14 +99,36 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const Args SA) {
   // ---- outputs: flat = [R(t5..), P(t0..), the first n phospho columns = masks 1 .. n] (randmod.py:298-299) and its parameter derivatives
   const int T5 = T > 5 ? T - 5 : 0;
   double* const fl = A.flat + rep * F;
-  double* const dfl = SA.dflat + rep * (long long)F * P;
+  double* const dfl = sens_dflat(SA) + rep * (long long)F * P;
   // metric flavour: thread it < NIT owns the (observed row, column) item it = row KC + c: its two sums (metric_acc), and the state value
   // and the column's entry at the previous output time, stay in its registers (no LDS beyond the plain flavour's: the workgroups per CU
   // are bounded by LDS here); mC = the shift, formed by every thread for itself
   constexpr int NIT = (2 + NB) * KC;
   static_assert(NIT <= NT, "one output item per thread");
   double mA = 0.0, mB = 0.0, mV = 0.0, mR = 0.0, mC = 0.0;
+  // VJP flavour: the same items; mA = the item's running sum (the value terms in the state column, c_f d_fp in a tangent column), c_f
+  // from the chunk's own state column
+  const VjpRow vr = vjp_row(SA, rep, F);
   auto emit = [&](const int k, const bool nan_fill) __attribute__((always_inline)) {
+    if constexpr (VJP) {                                          // the flat index is the sum index: no slot, no term
+      if (tid < NIT) {
+        const int row = tid / KC, c = tid % KC;
+        const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
+        if (fi >= 0) {
+          const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
+          const double qnan = __builtin_nan("");
+          const double yv = Y[row * KC];
+          const double sv = nan_fill ? qnan : ((A.clip && yv < 0.0) ? 0.0 : yv * sc);
+          const bool clipped = A.clip && (yv < (c == 0 ? 0.0 : -A.atol));
+          const double v = nan_fill ? qnan : (clipped ? 0.0 : Y[row * KC + c] * sc);
+          if (c == 0 && ch == 0 && A.flat) fl[fi] = v;
+          double term;
+          const double cf = vjp_entry(vr, fi, sv, term);
+          mA = (c == 0) ? mA + term : __builtin_fma(cf, v, mA);
+        }
+      }
+      return;
+    }
     if constexpr (MET) {                                          // every observed row enters the sums, the mRNA row at k < 5 (fi < 0) too
       auto post = [&](const int row) __attribute__((always_inline)) {
         const double yv = Y[row * KC];
@@ -147,6 +169,19 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const Args SA) {
     }
   };
   auto finish = [&](const int status, const int acc, const int rej) __attribute__((always_inline)) {
+    if constexpr (VJP) {                                          // across the workgroup through LDS (the error vector's, idle here): thread c sums column c over the rows, in row order
+      double* const sA = ER;
+      __syncthreads();
+      if (tid < NIT) sA[tid] = mA;
+      __syncthreads();
+      if (tid < KC) {
+        const int c = tid, p = pcol(c);
+        double a = 0.0;
+        for (int row = 0; row < 2 + NB; ++row) a += sA[row * KC + c];
+        if (c == 0) { if (ch == 0) SA.value[rep] = vr.tg ? 0.5 * a : a; }
+        else if (p >= 0) SA.grad[rep * P + p] = a;
+      }
+    }
     if constexpr (MET) {                                          // across the workgroup through LDS (the error vector's, idle here): thread c sums column c over the rows, in row order
       double* const sA = ER; double* const sB = ER + NIT;
       __syncthreads();

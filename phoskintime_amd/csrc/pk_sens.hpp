@@ -40,6 +40,43 @@ struct SensMetricArgs {
 };
 template <class Args> constexpr bool sens_metric_flavour() { return std::is_same<Args, SensMetricArgs>::value; }
 
+// The VJP flavour of the output stage, the third one selected by the argument type: a weighted sum over the FLAT entries and its gradient,
+//   linear mode        (target null):  c_f = w_f,                            value = sum_f w_f v_f,      grad_p = sum_f c_f d_fp
+//   least-squares mode (target set):   r_f = w_f (v_f - target_f), c_f = w_f r_f,  value = 1/2 sum_f r_f^2,  grad_p = sum_f c_f d_fp
+// v_f = the post-processed value flat stores, d_fp = the post-processed derivative dflat would store.  The sum index is the flat index:
+// the mRNA row at the first five output times has no slot and contributes nothing (the metric flavour sums it).  dflat never exists;
+// s.flat is optional.  Every column forms c_f from the state value it sees (the group's published one / its chunk's own integration) and
+// keeps ONE running sum over its entries in emit order; no atomics, nothing depends on the batch around a replica.
+struct SensVjpArgs {
+  SolveArgs s;
+  const double* w;      // [F] | [B, F]
+  const double* target; // [F] | [B, F] | null
+  double* value;        // [B]
+  double* grad;         // [B, P]
+  int w_batched, target_batched;
+};
+template <class Args> constexpr bool sens_vjp_flavour() { return std::is_same<Args, SensVjpArgs>::value; }
+
+// where the derivative rows go (the VJP flavour has no such output), and a replica's weights and targets (tg null: linear mode)
+__device__ __forceinline__ double* sens_dflat(const SensArgs& a) { return a.dflat; }
+__device__ __forceinline__ double* sens_dflat(const SensMetricArgs& a) { return a.dflat; }
+__device__ __forceinline__ double* sens_dflat(const SensVjpArgs&) { return nullptr; }
+struct VjpRow { const double* w; const double* tg; };
+template <class Args>
+__device__ __forceinline__ VjpRow vjp_row(const Args& SA, const long long rep, const int F) {
+  if constexpr (sens_vjp_flavour<Args>())
+    return VjpRow{SA.w + (SA.w_batched ? rep * F : 0), SA.target ? SA.target + (SA.target_batched ? rep * F : 0) : nullptr};
+  else return VjpRow{nullptr, nullptr};
+}
+// One flat entry: returns c_f, the weight of the entry's derivative row; term = the entry's share of value (of 2 value in least-squares mode)
+__device__ __forceinline__ double vjp_entry(const VjpRow& vr, const int fi, const double v, double& term) {
+  const double w = vr.w[fi];
+  if (!vr.tg) { term = w * v; return w; }
+  const double r = w * (v - vr.tg[fi]);
+  term = r * r;
+  return w * r;
+}
+
 // One (row, output time) entry of the metric sums.  v: the post-processed state value, pv: the same at the previous output time, c: the
 // mean of v at t0 (the shift of Emitter::emit).  Every column keeps a = sum r and b = sum w x over the entries, r being the column's
 // entry (v itself in the state column, the post-processed tangent otherwise) and pr its value at the previous output time:
@@ -585,10 +622,11 @@ template <class Sys, int GP> constexpr size_t sens_metric_lds_bytes(bool dynamic
   return sens_lds_bytes<Sys, GP>() + (dynamics ? ((size_t)(64 / GP) * Sys::NOBS + (size_t)Sys::NOBS * 64) * sizeof(double) : 0);
 }
 
-// Args = SensArgs, or SensMetricArgs for the metric flavour of the output stage (s.metric / dmetric required, s.flat / dflat optional)
+// Args = SensArgs, SensMetricArgs for the metric flavour of the output stage (s.metric / dmetric required, s.flat / dflat optional), or
+// SensVjpArgs for the VJP flavour (w / value / grad required, target and s.flat optional)
 template <class Sys, int GP, class Args = SensArgs>
 __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const Args SA) {
-  constexpr bool MET = sens_metric_flavour<Args>();
+  constexpr bool MET = sens_metric_flavour<Args>(), VJP = sens_vjp_flavour<Args>();
   using Tab = ResolventTab<PK_METHOD_LRP12>;
   constexpr int NR = Sys::NR, NG = 64 / GP;
   const SolveArgs& A = SA.s;
@@ -623,7 +661,10 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const A
 
   const int T5 = T > 5 ? T - 5 : 0;
   double* const fl = A.flat + rep * F;
-  double* const dfl = SA.dflat + rep * (long long)F * P + (c - 1);
+  double* const dfl = sens_dflat(SA) + rep * (long long)F * P + (c - 1);
+  // VJP flavour: this column's running sum (the value terms in the base lane, c_f d_fp in a tangent lane), stored once in finish
+  const VjpRow vr = vjp_row(SA, rep, F);
+  double vS = 0.0;
   // metric flavour: this column's sums (metric_acc) and the shift; bpv = the group's post-processed state values at the previous output
   // time, prs = this lane's own entries there -- read by `dynamics` alone, and only a launch for that metric carries their LDS
   // (sens_metric_lds_bytes): the waves per CU of these kernels are bounded by LDS at several sizes
@@ -647,7 +688,21 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const A
       constexpr int i = decltype(ic)::value;
       if (i < S && i < 2 + n) {
         const int fi = (i == 0) ? (k >= 5 ? k - 5 : -1) : (i == 1 ? T5 + k : T5 + T + (i - 2) * T + k);
-        if constexpr (!MET) {
+        if constexpr (VJP) {
+          if (fi >= 0) {                                          // the flat index is the sum index: no slot, no term
+            const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
+            const double qnan = __builtin_nan("");
+            const double v = nan_fill ? qnan : ((A.clip && by[i] < 0.0) ? 0.0 : by[i] * sc);
+            const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
+            double r;
+            if (nan_fill) r = qnan;
+            else r = clipped ? 0.0 : y.template get<i>() * sc;
+            if (is_base && live && A.flat) fl[fi] = r;
+            double term;
+            const double cf = vjp_entry(vr, fi, v, term);        // every lane from the group's published state value
+            vS = is_base ? vS + term : __builtin_fma(cf, r, vS);
+          }
+        } else if constexpr (!MET) {
           if (fi >= 0 && live) {
             const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
             // the value is clipped below 0; its derivative is dropped only where the state is negative beyond the absolute tolerance: a state
@@ -684,6 +739,12 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const A
     }
   };
   auto finish = [&](const int status, const int acc, const int rej) {
+    if constexpr (VJP) {                                        // in-lane sums: one store per lane
+      if (live) {
+        if (is_base) SA.value[rep] = vr.tg ? 0.5 * vS : vS;
+        else if (is_tan) SA.grad[rep * P + (c - 1)] = vS;
+      }
+    }
     if constexpr (MET) {                                        // in-lane sums: one store per lane
       const double L = (double)T * (double)(2 + n);
       const double a0 = bcast<GP, 0>(mA), b0 = bcast<GP, 0>(mB);

@@ -44,10 +44,10 @@ __device__ __forceinline__ void row_coef_deriv(const int p, const int n, const i
   }
 }
 
-// Args = SensArgs, or SensMetricArgs (pk_sens.hpp) for the metric flavour of the output stage
+// Args = SensArgs, or SensMetricArgs / SensVjpArgs (pk_sens.hpp) for the metric / VJP flavour of the output stage
 template <int MODEL, int G, int KC, class Args = SensArgs>
 __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
-  constexpr bool MET = sens_metric_flavour<Args>();
+  constexpr bool MET = sens_metric_flavour<Args>(), VJP = sens_vjp_flavour<Args>();
   using Tab = ResolventTab<PK_METHOD_LRP12>;
   using Solver = typename SolverFor<MODEL, G, true>::type;
   constexpr int WPB = 256 / G, KT = KC - 1;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
   const bool observed = row < S && row < 2 + n;
   const double yscale = (A.normalize && row < S) ? 1.0 / y_init : 1.0;
   double* const fl = A.flat + rep * F;
-  double* const dfl = SA.dflat + rep * (long long)F * P + (long long)ch * KT;
+  double* const dfl = sens_dflat(SA) + rep * (long long)F * P + (long long)ch * KT;
   // metric flavour: the sums of this lane's row for the state column (index 0) and its KT tangents and the row's entries at the previous
   // output time live in thread-private LDS slots (3 KC per thread, touched only at the output times: the step loop keeps its registers
   // and its two waves per SIMD); mC = the shift
@@ -91,7 +91,33 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
   auto slotP = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[(2 * KC + k) * 256]; };
   double mC = 0.0;
   if constexpr (MET) static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = 0.0; slotB(k) = 0.0; slotP(k) = 0.0; });
+  // VJP flavour: the running sums of this lane's row -- the value terms (index 0) and c_f d_fp of its KT tangents -- in the first KC of the
+  // same slots (KC per thread); a chunk forms c_f from its own state column
+  const VjpRow vr = vjp_row(SA, rep, F);
+  if constexpr (VJP) static_for<KC>([&](auto kc) { slotA(decltype(kc)::value) = 0.0; });
   auto emit = [&](const int kk, const bool nan_fill) {
+    if constexpr (VJP) {                                   // the flat index is the sum index: no slot, no term
+      if (!observed) return;
+      const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
+      if (fi < 0) return;
+      const bool clipped = A.clip && (y[0] < 0.0);
+      const bool dropped = A.clip && (y[0] < -A.atol);
+      const double qnan = __builtin_nan("");
+      const double v = nan_fill ? qnan : (clipped ? 0.0 : y[0] * yscale);
+      if (ch == 0 && A.flat) fl[fi] = v;
+      double term;
+      const double cf = vjp_entry(vr, fi, v, term);
+      double sa[KC];                                         // all slots first: their latencies overlap
+      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; sa[k] = slotA(k); });
+      sa[0] += term;
+      static_for<KT>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const double d = nan_fill ? qnan : (dropped ? 0.0 : y[1 + k] * yscale);
+        sa[1 + k] = __builtin_fma(cf, d, sa[1 + k]);
+      });
+      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = sa[k]; });
+      return;
+    }
     if constexpr (MET) {                                   // every observed row enters the sums, the mRNA row at kk < 5 (fi < 0) too
       const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
       const bool clipped = A.clip && (y[0] < 0.0);
@@ -135,6 +161,15 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
     for (; kk < T; ++kk) emit(kk, true);
   };
   auto finish = [&](const int status, const int acc, const int rej) {
+    if constexpr (VJP) {                                   // across the G lanes of the group, column by column (rows beyond the observed ones hold zeros)
+      const double v0 = gsum<G>(slotA(0), lane);
+      static_for<KT>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const double gk = gsum<G>(slotA(1 + k), lane);
+        if (row == 0 && ch * KT + k < P) SA.grad[rep * P + ch * KT + k] = gk;
+      });
+      if (row == 0 && ch == 0) SA.value[rep] = vr.tg ? 0.5 * v0 : v0;
+    }
     if constexpr (MET) {                                   // across the G lanes of the group, column by column (rows beyond the observed ones hold zeros)
       const double L = (double)T * (double)(2 + n);
       const double a0 = gsum<G>(slotA(0), lane), b0 = gsum<G>(slotB(0), lane);
@@ -265,7 +300,7 @@ static hipError_t launch_sens_rows_one(const Args& a, hipStream_t st) {
     hipError_t e = hipMemsetAsync(a.s.status, 0, (size_t)a.s.B * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
   }
-  constexpr size_t lds = sens_metric_flavour<Args>() ? (size_t)3 * kSensRowsKC * 256 * sizeof(double) : 0;      // the metric flavour's slots
+  constexpr size_t lds = (sens_metric_flavour<Args>() ? 3 : sens_vjp_flavour<Args>() ? 1 : 0) * (size_t)kSensRowsKC * 256 * sizeof(double);      // the metric / VJP flavour's slots
   hipLaunchKernelGGL((sens_rows_kernel<MODEL, G, kSensRowsKC, Args>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return hipGetLastError();
 }

@@ -445,6 +445,59 @@ def fit_rows_sharded(model: str, num_psites: int, time_points, P0, init_cond, ta
                    n_launches=meta[2])
 
 
+def cost_and_grad_rows(model: str, num_psites: int, time_points, Pm, init_cond, target, sigma=None, lam=0.0, log_space: Optional[bool] = None,
+                       **solver_kw):
+    """``fit_rows_batch``'s cost and its gradient at the points ``Pm`` [R, P] of the fitted space, from ONE launch and without a Jacobian
+    in memory -- what ``scipy.optimize.minimize(jac=True)``, L-BFGS-B or a projected-gradient screen takes: ``(cost [R], grad [R, P])``
+    as GPU tensors, with ``cost = 0.5 |([flat(theta) ; lam / P * p**2] - [target ; 0]) / sigma|^2`` and ``grad = d cost / d p``.
+
+    The data rows are the least-squares mode of ``batch.solve_ode_vjp_batch`` (weights ``1 / sigma``); the ridge rows and the chain rule
+    ``d theta / d p = exp(p)`` of the log space are added here in closed form.  Shapes as ``fit_rows_batch``: init_cond [S] or [R, S];
+    target [Nd] or [R, Nd]; sigma None, [Nr] or [R, Nr] with Nr = Nd (+ P when any lam > 0); lam scalar or [R].  ``log_space`` defaults
+    to what ``build_free_bounds`` uses for the model (randmod: True).  A row whose solve was flagged has cost and gradient NaN (the fit
+    counts such a row's residuals 1e6 each; there is no gradient to go with that).  Raises ``PhoskinError`` where no sensitivity kernel
+    exists (``batch.sens_available``)."""
+    import torch
+    if log_space is None:
+        log_space = (model == "randmod")
+
+    def dev_f64(a, dev=None):                                                # inputs stay where they are until the launch has placed its outputs
+        a = a.to(dtype=torch.float64) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, float))
+        return a if dev is None else a.to(dev)
+
+    p = dev_f64(Pm)
+    if p.dim() == 1:
+        p = p.unsqueeze(0)
+    R, P = p.shape
+    tgt = dev_f64(target)
+    Nd = tgt.shape[-1]
+    lam_d = dev_f64(lam).broadcast_to((R,))
+    use_reg = bool((lam_d > 0.0).any())
+    Nr = Nd + (P if use_reg else 0)
+    if sigma is None:
+        w_data, isig_reg = torch.ones(Nd, dtype=torch.float64), None
+    else:
+        sig = dev_f64(sigma)
+        if sig.shape[-1] != Nr:
+            raise ValueError(f"sigma must hold {Nr} entries")
+        w_data = 1.0 / sig[..., :Nd]
+        isig_reg = 1.0 / sig[..., Nd:] if use_reg else None
+    theta = torch.exp(p) if log_space else p
+    res = batch.solve_ode_vjp_batch(model, theta, init_cond, num_psites, time_points, w_data.contiguous(), tgt.contiguous(), **solver_kw)
+    cost = res.value
+    dev = cost.device
+    p, lam_d = dev_f64(p, dev), dev_f64(lam_d, dev)
+    grad = res.grad * dev_f64(theta, dev) if log_space else res.grad         # chain rule of theta = exp(p)
+    if use_reg:
+        isig_reg = None if isig_reg is None else dev_f64(isig_reg, dev)
+        k = (lam_d / P)[:, None]
+        rr = k * p * p if isig_reg is None else k * p * p * isig_reg         # ridge residuals (lam / P) p^2 / sigma
+        cost = cost + 0.5 * (rr * rr).sum(dim=1)
+        drr = 2.0 * k * p if isig_reg is None else 2.0 * k * p * isig_reg
+        grad = grad + rr * drr
+    return cost, grad
+
+
 def _pcov(JTJ_b, cost_b, absolute_sigma, Nr):
     """(J^T J)^-1 [* s^2] as scipy.optimize.curve_fit reports it."""
     P = JTJ_b.shape[0]
