@@ -22,6 +22,9 @@
 //     row R, then one subtraction per row; 1 / gamma is folded into the tableau weights at compile time.  The site sum that closes
 //     row P, its only reader the right-hand side, is formed in the prologue (initial step estimate) and in the cold non-finite test.
 //     A stage costs exactly ONE group reduction (inside the arrow solve); all of them are DPP moves only;
+//   * LRP8 and LRP12 take their error estimate as a repeated difference: two solves, then NS - 2 stages v <- v - M^{-1} v, each cheaper than a
+//     solve (one multiply and one FMA per row, the group sum's input from a sum carried from stage to stage); y_new is summed in that basis
+//     (ResolventTab::BN) and the estimate is the last v times E_2 / gamma -- no second accumulation.  RODAS4 keeps both weighted sums;
 //   * no LDS-pipe instruction in the solve chain; LDS only as thread-private parking space in the PARK layouts (below).
 //
 // pk_dist_rows.hpp holds the rows a lane carries (Stg) and what is done for every row of a lane -- the vector updates, both error norms,
@@ -451,7 +454,13 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // into the group sum) and nothing is inverted on its own.  Row 0 enters that sum as r_0 ws0 with ws0 = winv_0 w0 (C / (1 + q B) | 1 / q |
   // winv_0), and qs = q sinv is the sum's one multiplier.  So that a solve needs no select for the P slot, whose result is x_P itself,
   // lane 1 ends factor() with winv_0 = 0 and cw_0 = 1: fma(cw_0, x_P, r_P winv_0) is x_P (after Scw, to which the slot adds nothing).
-  double winv[RPL], cw[RPL], winvR, sinv, Scw, qq, qs, ws0;
+  // For the difference stages of LRP8 / LRP12 (below) a row also keeps omw_j = 1 - winv_j, and the lane Cl, the sum of cw over the rows its
+  // tracked sum runs over (every site row; resident: rows 1 .. RPL - 1, before the P slot's fixup -- row 0 never enters).  omw is formed as
+  // (q winv_j) d_j with d_j the diagonal entry (pivot 1 + q d_j), NOT as 1 - winv_j: on the first steps of a run q d_j is 1e-7 .. 1e-13 and the
+  // subtraction would keep nine to three digits of it, where the product is good to two ulps.  It costs the same: q winv_j is shared with
+  // cw_j = (q winv_j) S_j, one multiply more per row than cw alone instead of one add.  The R slot's d is B; the P slot takes omw = 1
+  // (v' = v - x_P) with its other fixups; shadowed, omwR = (q winvR) B and row P subtracts x_P itself.
+  double winv[RPL], cw[RPL], omw[RPL], winvR, omwR, Cl, sinv, Scw, qq, qs, ws0;
   auto factor = [&](const double q) {
     qq = q;
     constexpr int X = RES ? 0 : 1;
@@ -482,18 +491,39 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     }
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      cw[j] = q * pk.template get<K_SR + j>() * winv[j];
+      if constexpr (Tab::DIFFERENCE) {
+        const double qw = q * winv[j];
+        cw[j] = qw * pk.template get<K_SR + j>();
+        omw[j] = qw * pk.template get<K_DG + j>();
+      } else cw[j] = q * pk.template get<K_SR + j>() * winv[j];
     });
-    Scw = gsum<G>(tree_sum(cw), lane);
+    if constexpr (!Tab::DIFFERENCE) Scw = gsum<G>(tree_sum(cw), lane);
+    else if constexpr (!RES) {
+      omwR = q * winvR * cB;
+      Cl = tree_sum(cw);
+      Scw = gsum<G>(Cl, lane);
+    } else if constexpr (RPL > 1) {
+      double rest[RPL - 1];
+#pragma unroll
+      for (int j = 1; j < RPL; ++j) rest[j - 1] = cw[j];
+      Cl = tree_sum(rest);
+      Scw = gsum<G>(Cl + cw[0], lane);
+    } else {
+      Cl = 0.0;
+      Scw = gsum<G>(cw[0], lane);
+    }
     sinv = fast_rcp(__builtin_fma(q, Dsum - Scw, 1.0));
     if constexpr (RES) {
       qs = q * sinv;
       ws0 = winv[0] * w0;
       winv[0] = isP ? 0.0 : winv[0];
       cw[0] = isP ? 1.0 : cw[0];
+      if constexpr (Tab::DIFFERENCE) omw[0] = isP ? 1.0 : omw[0];
     }
   };
-  // u = M^{-1} r: ONE group reduction
+  // u = M^{-1} r: ONE group reduction.  lam (difference stages): the sum of u over the lane's tracked rows, from the sum of t the solve
+  // forms anyway: sum_j u_j = x_P Cl + sum_j t_j
+  double lam = 0.0;
   auto solve = [&](const Vec& r) {
     Vec u;
     double xR = 0.0;
@@ -503,31 +533,71 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     for (int j = 0; j < RPL; ++j) t[j] = r.s[j] * winv[j];
     if constexpr (RES) {
       // row 0 adds C x_R in lane 0 and r_P / q in lane 1: the group sum is C x_R + r_P / q + sum t_i, and x_P = sinv (r_P + q (C x_R + sum t_i))
-      double in;
+      double in, tsum = 0.0;
       if constexpr (RPL > 1) {
         double rest[RPL - 1];
 #pragma unroll
         for (int j = 1; j < RPL; ++j) rest[j - 1] = t[j];
-        in = __builtin_fma(r.s[0], ws0, tree_sum(rest));
+        tsum = tree_sum(rest);
+        in = __builtin_fma(r.s[0], ws0, tsum);
       } else in = r.s[0] * ws0;
       const double xP = gsum<G>(in, lane) * qs;
+      if constexpr (Tab::DIFFERENCE && RPL > 1) lam = __builtin_fma(xP, Cl, tsum);
       // uniform over the lanes: cw is 0 in the R slot (x_R = t), and 1 over t = 0 in the P slot (x_P)
 #pragma unroll
       for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
     } else {
-      const double St = gsum<G>(tree_sum(t), lane);
+      const double tsum = tree_sum(t);
+      const double St = gsum<G>(tsum, lane);
       const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), r.P()) * sinv;
+      if constexpr (Tab::DIFFERENCE) lam = __builtin_fma(xP, Cl, tsum);
 #pragma unroll
       for (int j = 0; j < RPL; ++j) u.s[j] = __builtin_fma(cw[j], xP, t[j]);
       u.R() = xR; u.P() = xP;
     }
     return u;
   };
+  // v <- v - M^{-1} v, one difference stage of LRP8 / LRP12, cheaper than a solve and a subtraction.  Every row of a solve obeys
+  // u_j = cw_j x_P + winv_j r_j (resident: the R and P slots too, after factor()'s fixups), so v'_j = omw_j v_j - cw_j x_P, uniformly over
+  // the lanes; and the group sum that feeds x_P needs sum winv_j v_j = lam - sum omw_j v_j with lam = sum v_j carried from stage to stage
+  // by one FMA, lam' = sum p_j - x_P Cl (p_j = omw_j v_j), instead of a second tree.  Resident: row 0 keeps its explicit term v_0 ws0 as
+  // in solve(), and lam, the tree and Cl run over rows 1 .. RPL - 1 (none of them at one row per lane).
+  auto diff = [&](Vec& v) {
+    double p[RPL];
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) p[j] = omw[j] * v.s[j];
+    if constexpr (RES) {
+      double in, psum = 0.0;
+      if constexpr (RPL > 1) {
+        double rest[RPL - 1];
+#pragma unroll
+        for (int j = 1; j < RPL; ++j) rest[j - 1] = p[j];
+        psum = tree_sum(rest);
+        in = __builtin_fma(v.s[0], ws0, lam - psum);
+      } else in = v.s[0] * ws0;
+      const double xP = gsum<G>(in, lane) * qs;
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) v.s[j] = __builtin_fma(-cw[j], xP, p[j]);
+      if constexpr (RPL > 1) lam = __builtin_fma(-xP, Cl, psum);
+    } else {
+      const double psum = tree_sum(p);
+      const double xR = v.R() * winvR;
+      const double St = gsum<G>(lam - psum, lane);
+      const double xP = __builtin_fma(qq, __builtin_fma(cC, xR, St), v.P()) * sinv;
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) v.s[j] = __builtin_fma(-cw[j], xP, p[j]);
+      lam = __builtin_fma(-xP, Cl, psum);
+      v.R() *= omwR; v.P() -= xP;
+    }
+  };
 
   // resolvent-form step (the right-hand side is affine, f(y) = J y + b with b = A in row R): z_1 = M^{-1} h f(y), z_{k+1} = M^{-1} z_k,
   //   y_new = y + sum_k B_k z_k ,  err = sum_k E_k z_k     (ResolventTab: RODAS4, LRP8 or LRP12)
   // With J = (I - M) / q the first stage needs no right-hand side: gamma z_1 = M^{-1} (y + q b) - y.  The loop carries w_k = gamma z_k
   // (w_{k+1} = M^{-1} w_k) and the weights B_k / gamma, E_k / gamma, divided at compile time.
+  // LRP8 and LRP12 (Tab::DIFFERENCE, pk_solve_kernel.hpp) take the two solves w_1, w_2 and then NS - 2 difference stages v_0 = w_2,
+  // v_{m+1} = v_m - M^{-1} v_m (diff(), above): y_new = y + (B_1 w_1 + sum_m BN_m v_m) / gamma, and the error estimate is the last v times
+  // E_2 / gamma -- no second accumulation; the factor multiplies the reduced norm once.  RODAS4 keeps both weighted sums.
   bool after_reject = false;
   // the non-finite test's view of the ACCEPTED state: R, P and the site sum, reduced over the group.  The step loop carries no site
   // sum, so this cold path forms it from the accepted rows -- in the parked layouts read back from their slots, since y.s holds the
@@ -593,17 +663,28 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         trk_axpy(z, -1.0, y);
       }
       Vec yn = y; trk_axpy(yn, Tab::B[0] / Tab::GAM, z);
-      Vec u6;
-      static_for<Tab::NS - 1>([&](auto kc) {
-        constexpr int kk = 1 + decltype(kc)::value;
-        constexpr double bk = Tab::B[kk] / Tab::GAM, ek = Tab::E[kk] / Tab::GAM;
-        z = solve(z);
-        trk_axpy(yn, bk, z);
-        if constexpr (kk == 1) u6 = trk_scale(ek, z); else trk_axpy(u6, ek, z);
-      });
-
       double err;
-      if constexpr (CFG::LITERAL) err = norm.group_max(u6, y, yn); else err = norm.err_norm(u6, y, yn);
+      if constexpr (Tab::DIFFERENCE) {
+        z = solve(z);
+        trk_axpy(yn, Tab::BN[0] / Tab::GAM, z);
+        static_for<Tab::NS - 2>([&](auto mc) {
+          constexpr int m = 1 + decltype(mc)::value;
+          diff(z);
+          trk_axpy(yn, Tab::BN[m] / Tab::GAM, z);
+        });
+        constexpr double e1 = (Tab::E[1] < 0.0 ? -Tab::E[1] : Tab::E[1]) / Tab::GAM;
+        if constexpr (CFG::LITERAL) err = e1 * norm.group_max(z, y, yn); else err = e1 * norm.err_norm(z, y, yn);
+      } else {
+        Vec u6;
+        static_for<Tab::NS - 1>([&](auto kc) {
+          constexpr int kk = 1 + decltype(kc)::value;
+          constexpr double bk = Tab::B[kk] / Tab::GAM, ek = Tab::E[kk] / Tab::GAM;
+          z = solve(z);
+          trk_axpy(yn, bk, z);
+          if constexpr (kk == 1) u6 = trk_scale(ek, z); else trk_axpy(u6, ek, z);
+        });
+        if constexpr (CFG::LITERAL) err = norm.group_max(u6, y, yn); else err = norm.err_norm(u6, y, yn);
+      }
       // accept / reject / landing bookkeeping on per-lane predicates (selects, and LDS writes under the lane mask); a NaN or inf error is
       // a rejection too (acc = false), so the state is settled before the non-finite exit below looks at it
       const bool acc = (err <= 1.0);

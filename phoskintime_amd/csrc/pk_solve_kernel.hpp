@@ -48,7 +48,18 @@ constexpr double RE2 = -0.27896255898136486925, RE3 = 0.80616997401331598084, RE
 // Resolvent-form one-step methods for affine systems:  M = I - GAM h J, z_1 = M^{-1} h f(y_n), z_{k+1} = M^{-1} z_k,
 //   y_{n+1} = y_n + sum_k B[k] z_k ,  err = sum_k E[k] z_k ,  step-size exponent 1 / Q  (Q = order of the estimator + 1).
 template <int METHOD> struct ResolventTab;
+//
+// DIFFERENCE: the estimator's weights are E[1] times a row of Pascal's triangle with alternating signs, E[k] = E[1] (-1)^(k-1) C(NS - 2, k - 1)
+// (k = 1 .. NS - 1, 0-based), so  err = E[1] (I - M^{-1})^(NS-2) z_2 : E[1] times the (NS - 2)-th difference of the stage sequence from z_2
+// on.  True of LRP8 and LRP12 by construction (the embedded method drops z_NS and loses one order: tools/restricted_pade.py --newton prints
+// the defect, 1e-52), not of RODAS4.  Such a table also carries BN, the weights of y_{n+1} in the difference basis
+//   v_0 = z_2, v_{m+1} = v_m - M^{-1} v_m :   y_{n+1} = y_n + B[0] z_1 + sum_{m=0}^{NS-2} BN[m] v_m ,   err = E[1] v_{NS-2} ,
+//   BN[m] = (-1)^m sum_{k >= m+1} B[k] C(k - 1, m)   (0-based k),  BN[NS - 2] = B[NS - 1] = E[1].
+// BN is printed from the 60-digit B by tools/restricted_pade.py --newton; summing the double-precision B here would lose the digits the
+// alternating B cancels (five of them at NS = 12: sum |B| = 926 against sum |BN| = 6.8).  dist_fast_kernel steps in this basis
+// (pk_dist_fast.hpp); the other kernels that read these tables use B and E.
 template <> struct ResolventTab<PK_METHOD_RODAS4> {          // RODAS4 rewritten for affine f (tools/rodas4_resolvent.py)
+  static constexpr bool DIFFERENCE = false;
   static constexpr int NS = 6;
   static constexpr double GAM = 0.25;
   static constexpr double Q = 4.0;
@@ -66,6 +77,9 @@ template <> struct ResolventTab<PK_METHOD_LRP8> {
                                   -11.197471732915163878, 6.15403680296552740685, -1.75732530837770792816, 0.207496723968028089083};
   static constexpr double E[8] = {0.0, 0.207496723968028089083, -1.2449803438081685345, 3.11245085952042133624,
                                   -4.14993447936056178166, 3.11245085952042133624, -1.2449803438081685345, 0.207496723968028089083};
+  static constexpr bool DIFFERENCE = true;
+  static constexpr double BN[7] = {0.78, -0.49272727272727272727, -0.59465564738292011019, 0.0046431254695717505635,
+                                   0.47986112059740910229, 0.51234496456953939366, 0.20749672396802808908};
 };
 
 // LRP12: 12 resolvent solves, order 11, embedded order 10 on z_1..z_11; gamma = 0.16.  R(inf) = 0 (L-stable); the embedded method is
@@ -74,6 +88,8 @@ template <> struct ResolventTab<PK_METHOD_LRP8> {
 // restricted_pade.py 12 0.16; tests/test_integrator_tables.py).  For comparison the reference's LSODA switches to BDF1-5 (alpha = 73 deg
 // at order 4, 51 deg at order 5).  The models' Jacobians are (similar to) M-matrices with real spectra, where only |R(x)| <= 1, x <= 0, matters.  Weights alternate in sign up to ~240: three digits of cancellation
 // against double precision's sixteen, five orders of magnitude below the parity band.
+// (That is the weighted sum over B, which the kernels other than dist_fast_kernel take; in the difference basis BN the weights stay below 1.3
+// and nothing cancels.)
 template <> struct ResolventTab<PK_METHOD_LRP12> {
   static constexpr int NS = 12;
   static constexpr double GAM = 0.16;
@@ -84,6 +100,10 @@ template <> struct ResolventTab<PK_METHOD_LRP12> {
   static constexpr double E[12] = {0.0, 0.7300070952791203973919, -7.300070952791203973919, 32.85031928756041788264, -87.60085143349444768703,
                                    153.3014900086152834523, -183.9617880103383401428, 153.3014900086152834523, -87.60085143349444768703,
                                    32.85031928756041788264, -7.300070952791203973919, 0.7300070952791203973919};
+  static constexpr bool DIFFERENCE = true;
+  static constexpr double BN[11] = {0.84, -1.285, -0.024583333333333333333, 0.959140625, 0.54719401041666666667, -0.36608859592013888889,
+                                    -0.82203744070870535714, -0.5787759293450249566, 0.039384253912291619303, 0.57111326014869427555,
+                                    0.73000709527912039739};
 };
 
 // err^(1/Q) for the step-size controller: single precision is ample (the factor is clamped to [1/6, 5] anyway)

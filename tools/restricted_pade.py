@@ -47,8 +47,21 @@ def a_stable(beta, gamma, n=4000):
         worst = max(worst, abs(R(beta, gamma, mp.mpc(0, y))))
     return worst
 
+def newton_weights(beta):
+    """y_{n+1} - y_n = beta_1 z_1 + sum_m bn_m v_m in the difference basis v_0 = z_2, v_{m+1} = v_m - M^{-1} v_m, m = 0..s-2:
+    z_k = (I - D)^(k-2) z_2 with D = I - M^{-1}, so bn_m = (-1)^m sum_{k >= m+2} beta_k C(k-2, m) (beta_k 1-based)."""
+    s = len(beta)
+    return [(-1) ** m * sum(beta[k - 1] * mp.binomial(k - 2, m) for k in range(m + 2, s + 1)) for m in range(s - 1)]
+
+def difference_defect(eps):
+    """Largest |eps_k - eps_2 (-1)^k C(s-2, k-2)| / |eps_2|, k = 2..s: zero when the estimate is eps_2 times the (s-2)-th difference of z_2."""
+    s = len(eps)
+    return max(abs(eps[k - 1] - eps[1] * (-1) ** k * mp.binomial(s - 2, k - 2)) for k in range(2, s + 1)) / abs(eps[1])
+
 if __name__ == '__main__':
     import sys
+    newton = '--newton' in sys.argv                # also print the difference-basis weights (ResolventTab::BN), 60-digit arithmetic
+    sys.argv = [a for a in sys.argv if a != '--newton']
     s = int(sys.argv[1]) if len(sys.argv) > 1 else 6
     for gs in (sys.argv[2:] or ['0.2', '0.25', '0.3']):
         g = mp.mpf(gs)
@@ -62,3 +75,6 @@ if __name__ == '__main__':
         print('s=%d gamma=%s  max|R(iy)|=%s  max|Rhat(iy)|=%s  err const C_%d=%s  Chat_%d=%s' % (s, gs, mp.nstr(a_stable(beta, g), 8), mp.nstr(a_stable(bh, g), 8), s, mp.nstr(ec, 5), s - 1, mp.nstr(ech, 5)))
         print('   beta =', [mp.nstr(x, 22) for x in beta])
         print('   eps  =', [mp.nstr(x - y, 22) for x, y in zip(beta, bh)])
+        if newton:
+            print('   BN   =', [mp.nstr(x, 20) for x in newton_weights(beta)])
+            print('   eps_k = eps_2 (-1)^k C(s-2, k-2): defect %s' % mp.nstr(difference_defect([x - y for x, y in zip(beta, bh)]), 5))
