@@ -11,7 +11,7 @@
 #include "../../include/phoskin.h"
 #include "pk_launch.hpp"
 #include "pk_plan.hpp"
-#include "pk_sens.hpp"
+#include "pk_sens_out.hpp"
 
 // A growable device buffer that outlives calls: the `_host` entry points stage through one, kernels that need per-replica HBM scratch
 // use another (two, so that an inner device-pointer call can never move the staging area of the `_host` call around it).
@@ -441,6 +441,30 @@ struct HostCall {
     return download();
   }
 };
+
+constexpr const char* kSensUnsupported = "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)";
+
+// The checks that the three flavours of pk_solve_protein_sens*_batch share; callers rely on their order.  metric_id: the
+// metric flavour's, checked between the size and the empty batch (null: no such argument); have_ptrs / ptrs_msg: the flavour's own
+// required pointers.  Returns kSensGo with the resolved options in `o`, or what the entry point returns: an error, or PK_OK for B = 0.
+constexpr int kSensGo = 1;
+int sens_prologue(pk_ctx* c, int model, int n_sites, int64_t B, int T, const int* metric_id, bool have_ptrs, const char* ptrs_msg,
+                  const pk_solver_opts* opts_in, pk_solver_opts& o) {
+  if (!c) return PK_ERR_ARG;
+  int rc = check_model(c, model, n_sites);
+  if (rc) return rc;
+  if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
+  if (T < 1) return fail(c, PK_ERR_ARG, "T must be >= 1");
+  if (!pk::sens_available(model, n_sites)) return fail(c, PK_ERR_UNSUPPORTED, kSensUnsupported);
+  if (metric_id && (*metric_id < PK_METRIC_TOTAL_SIGNAL || *metric_id > PK_METRIC_L2_NORM)) return fail(c, PK_ERR_ARG, "unknown metric_id");
+  if (B == 0) return PK_OK;
+  if (!have_ptrs) return fail(c, PK_ERR_ARG, ptrs_msg);
+  o = solver_opts(opts_in);
+  if (o.method != PK_METHOD_LRP12 || o.stage_form) return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities integrate with method LRP12 (the default) only");
+  if (!(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
+  if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
+  return kSensGo;
+}
 }  // namespace
 extern "C" {
 
@@ -451,22 +475,12 @@ int pk_protein_sens_available(int model, int n_sites) {
 int pk_solve_protein_sens_batch(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched,
                                 const double* t, int T, const pk_solver_opts* opts_in, double* flat, double* dflat, int32_t* status,
                                 int32_t* n_steps) {
-  if (!c) return PK_ERR_ARG;
-  int rc = check_model(c, model, n_sites);
-  if (rc) return rc;
-  if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
-  if (T < 1) return fail(c, PK_ERR_ARG, "T must be >= 1");
-  if (!pk::sens_available(model, n_sites))
-    return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)");
-  if (B == 0) return PK_OK;
-  if (!theta || !y0 || !t || !flat || !dflat) return fail(c, PK_ERR_ARG, "theta, y0, t, flat and dflat must be non-null");
-  const pk_solver_opts o = solver_opts(opts_in);
-  if (o.method != PK_METHOD_LRP12 || o.stage_form) return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities integrate with method LRP12 (the default) only");
-  if (!(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
+  pk_solver_opts o;
+  const int rc = sens_prologue(c, model, n_sites, B, T, nullptr, theta && y0 && t && flat && dflat, "theta, y0, t, flat and dflat must be non-null", opts_in, o);
+  if (rc != kSensGo) return rc;
   pk::SensArgs sa;              // no trajectory and no metric: the observables and their derivatives (stage_form is 0 here)
   sa.s = solve_args(model, n_sites, B, theta, y0, y0_is_batched, t, T, o, nullptr, flat, nullptr, 0, status, n_steps);
   sa.dflat = dflat;
-  if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, pk::launch_sens(sa, model, c->stream));
   return PK_OK;
@@ -475,24 +489,13 @@ int pk_solve_protein_sens_batch(pk_ctx* c, int model, int n_sites, int64_t B, co
 int pk_solve_protein_sens_metric_batch(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched,
                                        const double* t, int T, const pk_solver_opts* opts_in, int metric_id, double* metric, double* dmetric,
                                        double* flat, double* dflat, int32_t* status, int32_t* n_steps) {
-  if (!c) return PK_ERR_ARG;
-  int rc = check_model(c, model, n_sites);
-  if (rc) return rc;
-  if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
-  if (T < 1) return fail(c, PK_ERR_ARG, "T must be >= 1");
-  if (!pk::sens_available(model, n_sites))
-    return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)");
-  if (metric_id < PK_METRIC_TOTAL_SIGNAL || metric_id > PK_METRIC_L2_NORM) return fail(c, PK_ERR_ARG, "unknown metric_id");
-  if (B == 0) return PK_OK;
-  if (!theta || !y0 || !t || !metric || !dmetric) return fail(c, PK_ERR_ARG, "theta, y0, t, metric and dmetric must be non-null");
-  const pk_solver_opts o = solver_opts(opts_in);
-  if (o.method != PK_METHOD_LRP12 || o.stage_form) return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities integrate with method LRP12 (the default) only");
-  if (!(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
+  pk_solver_opts o;
+  const int rc = sens_prologue(c, model, n_sites, B, T, &metric_id, theta && y0 && t && metric && dmetric, "theta, y0, t, metric and dmetric must be non-null", opts_in, o);
+  if (rc != kSensGo) return rc;
   pk::SensMetricArgs sa;        // the metric flavour of the output stage: flat / dflat may be null
   sa.s = solve_args(model, n_sites, B, theta, y0, y0_is_batched, t, T, o, nullptr, flat, metric, metric_id, status, n_steps);
   sa.dflat = dflat;
   sa.dmetric = dmetric;
-  if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, pk::launch_sens_metric(sa, model, c->stream));
   return PK_OK;
@@ -501,24 +504,14 @@ int pk_solve_protein_sens_metric_batch(pk_ctx* c, int model, int n_sites, int64_
 int pk_solve_protein_sens_vjp_batch(pk_ctx* c, int model, int n_sites, int64_t B, const double* theta, const double* y0, int y0_is_batched,
                                     const double* t, int T, const pk_solver_opts* opts_in, const double* w, int w_is_batched, const double* target,
                                     int target_is_batched, double* value, double* grad, double* flat, int32_t* status, int32_t* n_steps) {
-  if (!c) return PK_ERR_ARG;
-  int rc = check_model(c, model, n_sites);
-  if (rc) return rc;
-  if (B < 0) return fail(c, PK_ERR_ARG, "B must be >= 0");
-  if (T < 1) return fail(c, PK_ERR_ARG, "T must be >= 1");
-  if (!pk::sens_available(model, n_sites))
-    return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)");
-  if (B == 0) return PK_OK;
-  if (!theta || !y0 || !t || !w || !value || !grad) return fail(c, PK_ERR_ARG, "theta, y0, t, w, value and grad must be non-null");
-  const pk_solver_opts o = solver_opts(opts_in);
-  if (o.method != PK_METHOD_LRP12 || o.stage_form) return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities integrate with method LRP12 (the default) only");
-  if (!(o.rtol > 0.0 && o.atol >= 0.0)) return fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
+  pk_solver_opts o;
+  const int rc = sens_prologue(c, model, n_sites, B, T, nullptr, theta && y0 && t && w && value && grad, "theta, y0, t, w, value and grad must be non-null", opts_in, o);
+  if (rc != kSensGo) return rc;
   pk::SensVjpArgs sa;           // the VJP flavour of the output stage: flat may be null, target null selects the linear mode
   sa.s = solve_args(model, n_sites, B, theta, y0, y0_is_batched, t, T, o, nullptr, flat, nullptr, 0, status, n_steps);
   sa.w = w; sa.w_batched = w_is_batched ? 1 : 0;
   sa.target = target; sa.target_batched = (target && target_is_batched) ? 1 : 0;
   sa.value = value; sa.grad = grad;
-  if (B > 0x7fffffffLL) return fail(c, PK_ERR_ARG, "batch too large for one launch");
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, pk::launch_sens_vjp(sa, model, c->stream));
   return PK_OK;
@@ -555,8 +548,7 @@ int pk_solve_protein_sens_batch_host(pk_ctx* c, int model, int n_sites, int64_t 
   int rc = check_model(c, model, n_sites);
   if (rc) return rc;
   if (B < 0 || T < 1) return fail(c, PK_ERR_ARG, "B must be >= 0 and T >= 1");
-  if (!pk::sens_available(model, n_sites))
-    return fail(c, PK_ERR_UNSUPPORTED, "forward sensitivities: distmod / succmod n_sites <= 62, randmod n_sites <= 7 (difference the batched solve beyond)");
+  if (!pk::sens_available(model, n_sites)) return fail(c, PK_ERR_UNSUPPORTED, kSensUnsupported);
   if (B == 0) return PK_OK;
   if (!theta || !y0 || !t || !flat || !dflat) return fail(c, PK_ERR_ARG, "theta, y0, t, flat and dflat must be non-null");
   const size_t S = pk::n_states(model, n_sites), P = pk::n_params(model, n_sites), F = pk_protein_flat_len(model, n_sites, T);

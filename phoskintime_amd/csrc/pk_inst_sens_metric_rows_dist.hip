@@ -2,5 +2,5 @@
 #include "pk_sens_rows.hpp"
 #include "pk_launch.hpp"
 namespace pk {
-hipError_t launch_sens_metric_rows_dist(const SensMetricArgs& a, hipStream_t st) { return launch_sens_rows_model<M_DIST>(a, st); }
+hipError_t launch_sens_rows_dist(const SensMetricArgs& a, hipStream_t st) { return launch_sens_rows_model<M_DIST>(a, st); }
 }  // namespace pk

@@ -2,5 +2,5 @@
 #include "pk_sens_rows.hpp"
 #include "pk_launch.hpp"
 namespace pk {
-hipError_t launch_sens_vjp_rows_succ(const SensVjpArgs& a, hipStream_t st) { return launch_sens_rows_model<M_SUCC>(a, st); }
+hipError_t launch_sens_rows_succ(const SensVjpArgs& a, hipStream_t st) { return launch_sens_rows_model<M_SUCC>(a, st); }
 }  // namespace pk

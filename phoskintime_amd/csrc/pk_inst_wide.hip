@@ -83,12 +83,12 @@ static hipError_t launch_rand_sens_any(const Args& a, hipStream_t st) {
   if (a.s.n_sites == 7) return launch_rand_sens_one<7>(a, st);
   return hipErrorInvalidValue;
 }
+// the three flavours of the output stage (pk_sens_out.hpp), overloads that launch_sens_any (pk_inst_sens.inc) calls.  All here and not
+// beside the other metric / VJP instantiations: pk_wide.hpp, which pk_rand_sens.hpp builds on, defines kernels that one translation unit
+// alone may hold
 hipError_t launch_rand_sens(const SensArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
-// its metric flavour (pk_sens.hpp, SensMetricArgs).  Here and not beside the other metric instantiations: pk_wide.hpp, which pk_rand_sens.hpp
-// builds on, defines kernels that one translation unit alone may hold
-hipError_t launch_rand_sens_metric(const SensMetricArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
-// and its VJP flavour (SensVjpArgs), here for the same reason
-hipError_t launch_rand_sens_vjp(const SensVjpArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
+hipError_t launch_rand_sens(const SensMetricArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
+hipError_t launch_rand_sens(const SensVjpArgs& a, hipStream_t st) { return launch_rand_sens_any(a, st); }
 
 bool rand_dense_available(int n_sites) {
   static const bool on = [] { const char* v = getenv("PK_WIDE_RAND_DENSE"); return !(v && v[0] == '0'); }();

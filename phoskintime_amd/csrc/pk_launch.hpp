@@ -32,7 +32,8 @@ void launch_rand_fast(const SolveArgs&, int method, hipStream_t);
 // thread-per-replica kernels for small distributive / successive systems (pk_tpr.hpp), LRP12
 bool tpr_available(int model, int n_sites);
 hipError_t launch_tpr(const SolveArgs&, int model, hipStream_t);   // sets the dynamic-LDS limit per device; its error is the caller's
-// forward parameter sensitivities, one column per lane (pk_sens.hpp), LRP12
+// forward parameter sensitivities, one column per lane (pk_sens.hpp), LRP12.  The three flavours of the output stage (pk_sens_out.hpp)
+// go through one size table, launch_sens_any in pk_inst_sens.inc
 struct SensArgs;
 bool sens_available(int model, int n_sites);
 hipError_t launch_sens(const SensArgs&, int model, hipStream_t);

@@ -31,7 +31,7 @@ __host__ __device__ constexpr size_t rand_sens_lds_bytes(int n) {
 }
 
 // TBP: side of the thread grid over the even Schur complement: 16 (256 threads) or 8 (n = 6: ONE wave per column chunk, 4 x 4 blocks per lane)
-// Args = SensArgs, or SensMetricArgs / SensVjpArgs (pk_sens.hpp) for the metric / VJP flavour of the output stage
+// Args = SensArgs, or SensMetricArgs / SensVjpArgs for the metric / VJP flavour of the output stage (pk_sens_out.hpp)
 template <int NB, int TBP = 16, class Args = SensArgs>
 __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const Args SA) {
   constexpr bool MET = sens_metric_flavour<Args>(), VJP = sens_vjp_flavour<Args>();
@@ -100,101 +100,55 @@ __global__ __launch_bounds__(TBP * TBP) void rand_sens_kernel(const Args SA) {
   const int T5 = T > 5 ? T - 5 : 0;
   double* const fl = A.flat + rep * F;
   double* const dfl = sens_dflat(SA) + rep * (long long)F * P;
-  // metric flavour: thread it < NIT owns the (observed row, column) item it = row KC + c: its two sums (metric_acc), and the state value
-  // and the column's entry at the previous output time, stay in its registers (no LDS beyond the plain flavour's: the workgroups per CU
-  // are bounded by LDS here); mC = the shift, formed by every thread for itself
-  constexpr int NIT = (2 + NB) * KC;
+  // thread it < NIT owns the (observed row, column) item it = row KC + c.  Metric / VJP flavour: the item's running sums
+  // (sens_accumulate; c_f from the chunk's own state column), and the state value and the column's entry at the previous output time,
+  // stay in its registers (no LDS beyond the plain flavour's: the workgroups per CU are bounded by LDS here); mC = the metric flavour's
+  // shift, formed by every thread for itself
+  constexpr int NIT = (2 + NB) * KC, NSUM = sens_sum_count<Args>();
   static_assert(NIT <= NT, "one output item per thread");
   double mA = 0.0, mB = 0.0, mV = 0.0, mR = 0.0, mC = 0.0;
-  // VJP flavour: the same items; mA = the item's running sum (the value terms in the state column, c_f d_fp in a tangent column), c_f
-  // from the chunk's own state column
   const VjpRow vr = vjp_row(SA, rep, F);
   auto emit = [&](const int k, const bool nan_fill) __attribute__((always_inline)) {
-    if constexpr (VJP) {                                          // the flat index is the sum index: no slot, no term
-      if (tid < NIT) {
-        const int row = tid / KC, c = tid % KC;
-        const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
-        if (fi >= 0) {
-          const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
-          const double qnan = __builtin_nan("");
-          const double yv = Y[row * KC];
-          const double sv = nan_fill ? qnan : ((A.clip && yv < 0.0) ? 0.0 : yv * sc);
-          const bool clipped = A.clip && (yv < (c == 0 ? 0.0 : -A.atol));
-          const double v = nan_fill ? qnan : (clipped ? 0.0 : Y[row * KC + c] * sc);
-          if (c == 0 && ch == 0 && A.flat) fl[fi] = v;
-          double term;
-          const double cf = vjp_entry(vr, fi, sv, term);
-          mA = (c == 0) ? mA + term : __builtin_fma(cf, v, mA);
-        }
-      }
-      return;
-    }
-    if constexpr (MET) {                                          // every observed row enters the sums, the mRNA row at k < 5 (fi < 0) too
-      auto post = [&](const int row) __attribute__((always_inline)) {
-        const double yv = Y[row * KC];
-        return (A.clip && yv < 0.0) ? 0.0 : yv * (A.normalize ? 1.0 / y0p[row] : 1.0);
-      };
+    if constexpr (MET) {
       if (k == 0) {
         double s0 = 0.0;
-        for (int row = 0; row < 2 + NB; ++row) s0 += post(row);
+        for (int row = 0; row < 2 + NB; ++row) s0 += sens_post_value(A, Y[row * KC], A.normalize ? 1.0 / y0p[row] : 1.0, false);
         mC = s0 / (double)(2 + NB);
       }
-      if (tid < NIT) {
-        const int row = tid / KC, c = tid % KC;
-        const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
-        const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
-        const double qnan = __builtin_nan("");
-        const double sv = nan_fill ? qnan : post(row);
-        const bool clipped = A.clip && (Y[row * KC] < (c == 0 ? 0.0 : -A.atol));
-        const double v = nan_fill ? qnan : (clipped ? 0.0 : Y[row * KC + c] * sc);
-        const int p = pcol(c);
-        if (fi >= 0) {
-          if (c == 0) { if (ch == 0 && A.flat) fl[fi] = v; }
-          else if (p >= 0 && SA.dflat) dfl[(long long)fi * P + p] = v;
-        }
-        metric_acc(A.metric_id, c == 0, k, metric_weight(A.metric_id, k, sv, mV, mC), v, mR, mA, mB);
-        mV = sv; mR = v;
-      }
-      return;
     }
-    for (int it = tid; it < (2 + NB) * KC; it += nt) {
-      const int row = it / KC, c = it % KC;
-      const int fi = (row == 0) ? (k >= 5 ? k - 5 : -1) : (row == 1 ? T5 + k : T5 + T + (row - 2) * T + k);
-      if (fi < 0) continue;
-      const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
-      const bool clipped = A.clip && (Y[row * KC] < (c == 0 ? 0.0 : -A.atol));      // derivative rows: negative beyond the absolute tolerance (pk_sens.hpp, emit)
-      const double v = nan_fill ? __builtin_nan("") : (clipped ? 0.0 : Y[row * KC + c] * sc);
-      if (c == 0) { if (ch == 0) fl[fi] = v; }
-      else { const int p = pcol(c); if (p >= 0) dfl[(long long)fi * P + p] = v; }
+    if (tid >= NIT) return;
+    const int row = tid / KC, c = tid % KC;
+    const int fi = sens_flat_index(row, k, T, T5);
+    if (!MET && fi < 0) return;                                   // the metric flavour sums every observed row, the mRNA row at k < 5 (fi < 0) too
+    const double sc = A.normalize ? 1.0 / y0p[row] : 1.0;
+    const double yv = Y[row * KC];
+    const double sv = sens_post_value(A, yv, sc, nan_fill);
+    const double v = sens_post_entry(A, yv, Y[row * KC + c], sc, c == 0, nan_fill);
+    if (fi >= 0) {
+      const int p = pcol(c);
+      if (c == 0) { if (ch == 0 && sens_writes_flat(SA)) fl[fi] = v; }
+      else if (p >= 0 && sens_writes_dflat(SA)) dfl[(long long)fi * P + p] = v;
     }
+    sens_accumulate(SA, sens_row_term(SA, vr, fi, k, sv, mV, mC), k, v, c == 0, mR, mA, mB);
+    mV = sv; mR = v;
   };
   auto finish = [&](const int status, const int acc, const int rej) __attribute__((always_inline)) {
-    if constexpr (VJP) {                                          // across the workgroup through LDS (the error vector's, idle here): thread c sums column c over the rows, in row order
-      double* const sA = ER;
-      __syncthreads();
-      if (tid < NIT) sA[tid] = mA;
-      __syncthreads();
-      if (tid < KC) {
-        const int c = tid, p = pcol(c);
-        double a = 0.0;
-        for (int row = 0; row < 2 + NB; ++row) a += sA[row * KC + c];
-        if (c == 0) { if (ch == 0) SA.value[rep] = vr.tg ? 0.5 * a : a; }
-        else if (p >= 0) SA.grad[rep * P + p] = a;
-      }
-    }
-    if constexpr (MET) {                                          // across the workgroup through LDS (the error vector's, idle here): thread c sums column c over the rows, in row order
+    if constexpr (NSUM >= 1) {                                    // across the workgroup through LDS (the error vector's, idle here): thread c sums column c over the rows, in row order
       double* const sA = ER; double* const sB = ER + NIT;
       __syncthreads();
-      if (tid < NIT) { sA[tid] = mA; sB[tid] = mB; }
+      if (tid < NIT) { sA[tid] = mA; if constexpr (NSUM == 2) sB[tid] = mB; }
       __syncthreads();
       if (tid < KC) {
         const int c = tid, p = pcol(c);
-        const double L = (double)T * (double)(2 + NB);
         double a0 = 0.0, b0 = 0.0, a = 0.0, b = 0.0;
-        for (int row = 0; row < 2 + NB; ++row) { a0 += sA[row * KC]; b0 += sB[row * KC]; a += sA[row * KC + c]; b += sB[row * KC + c]; }
-        const double m = metric_value(A.metric_id, a0, b0, mC, L);
-        if (c == 0) { if (ch == 0) A.metric[rep] = m; }
-        else if (p >= 0) SA.dmetric[rep * P + p] = metric_grad(A.metric_id, a, b, a0, m, mC, L);
+        for (int row = 0; row < 2 + NB; ++row) {
+          a0 += sA[row * KC]; a += sA[row * KC + c];
+          if constexpr (NSUM == 2) { b0 += sB[row * KC]; b += sB[row * KC + c]; }
+        }
+        const double L = (double)T * (double)(2 + NB);
+        const double m = sens_reduce_scalar(SA, vr, a0, b0, mC, L);
+        if (c == 0) { if (ch == 0) sens_scalar(SA)[rep] = m; }
+        else if (p >= 0) sens_grad(SA)[rep * P + p] = sens_reduce_grad(SA, a, b, a0, m, mC, L);
       }
     }
     if (tid != 0) return;

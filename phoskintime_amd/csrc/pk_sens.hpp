@@ -18,107 +18,9 @@
 // sequence is therefore shared by the group; clipping (y < 0 -> 0) zeroes the derivative like it zeroes the value.
 // One wave per workgroup, NG = 64 / GP replicas per wave; LDS: two thread-private coefficient sets + 2 S doubles per group.
 #pragma once
-#include <type_traits>
-#include "pk_solve_kernel.hpp"
+#include "pk_sens_out.hpp"
 
 namespace pk {
-
-struct SensArgs {
-  SolveArgs s;
-  double* dflat;        // [B, F, P]
-};
-
-// The metric flavour of the output stage (a compile-time flavour selected by the argument type, as NetScore selects the scoring flavours
-// of net_rosw_solve): besides flat / dflat -- both optional here, null = not written -- the kernels return the scalar Morris output
-// m = _compute_Y of the post-processed observables (s.metric [B], s.metric_id; Emitter::finish in pk_solve_kernel.hpp defines it) and its
-// gradient d m / d theta (dmetric [B, P]).  The sums run over ALL observed rows i < 2 + n_sites at ALL output times, the mRNA row at
-// k < 5 included, which has no slot in flat.
-struct SensMetricArgs {
-  SolveArgs s;
-  double* dflat;        // [B, F, P] | null
-  double* dmetric;      // [B, P]
-};
-template <class Args> constexpr bool sens_metric_flavour() { return std::is_same<Args, SensMetricArgs>::value; }
-
-// The VJP flavour of the output stage, the third one selected by the argument type: a weighted sum over the FLAT entries and its gradient,
-//   linear mode        (target null):  c_f = w_f,                            value = sum_f w_f v_f,      grad_p = sum_f c_f d_fp
-//   least-squares mode (target set):   r_f = w_f (v_f - target_f), c_f = w_f r_f,  value = 1/2 sum_f r_f^2,  grad_p = sum_f c_f d_fp
-// v_f = the post-processed value flat stores, d_fp = the post-processed derivative dflat would store.  The sum index is the flat index:
-// the mRNA row at the first five output times has no slot and contributes nothing (the metric flavour sums it).  dflat never exists;
-// s.flat is optional.  Every column forms c_f from the state value it sees (the group's published one / its chunk's own integration) and
-// keeps ONE running sum over its entries in emit order; no atomics, nothing depends on the batch around a replica.
-struct SensVjpArgs {
-  SolveArgs s;
-  const double* w;      // [F] | [B, F]
-  const double* target; // [F] | [B, F] | null
-  double* value;        // [B]
-  double* grad;         // [B, P]
-  int w_batched, target_batched;
-};
-template <class Args> constexpr bool sens_vjp_flavour() { return std::is_same<Args, SensVjpArgs>::value; }
-
-// where the derivative rows go (the VJP flavour has no such output), and a replica's weights and targets (tg null: linear mode)
-__device__ __forceinline__ double* sens_dflat(const SensArgs& a) { return a.dflat; }
-__device__ __forceinline__ double* sens_dflat(const SensMetricArgs& a) { return a.dflat; }
-__device__ __forceinline__ double* sens_dflat(const SensVjpArgs&) { return nullptr; }
-struct VjpRow { const double* w; const double* tg; };
-template <class Args>
-__device__ __forceinline__ VjpRow vjp_row(const Args& SA, const long long rep, const int F) {
-  if constexpr (sens_vjp_flavour<Args>())
-    return VjpRow{SA.w + (SA.w_batched ? rep * F : 0), SA.target ? SA.target + (SA.target_batched ? rep * F : 0) : nullptr};
-  else return VjpRow{nullptr, nullptr};
-}
-// One flat entry: returns c_f, the weight of the entry's derivative row; term = the entry's share of value (of 2 value in least-squares mode)
-__device__ __forceinline__ double vjp_entry(const VjpRow& vr, const int fi, const double v, double& term) {
-  const double w = vr.w[fi];
-  if (!vr.tg) { term = w * v; return w; }
-  const double r = w * (v - vr.tg[fi]);
-  term = r * r;
-  return w * r;
-}
-
-// One (row, output time) entry of the metric sums.  v: the post-processed state value, pv: the same at the previous output time, c: the
-// mean of v at t0 (the shift of Emitter::emit).  Every column keeps a = sum r and b = sum w x over the entries, r being the column's
-// entry (v itself in the state column, the post-processed tangent otherwise) and pr its value at the previous output time:
-//   variance   w = v - c,        x = r  (v - c in the state column: b = sum (v - c)^2)
-//   dynamics   w = v_k - v_k-1,  x = r_k - r_k-1  (nothing at k = 0)
-//   l2_norm    w = v,            x = r
-// The weight is the same for every column of a row: formed once per row and output time.
-__device__ __forceinline__ double metric_weight(const int metric_id, const int k, const double v, const double pv, const double c) {
-  switch (metric_id) {
-    case PK_METRIC_VARIANCE: return v - c;
-    case PK_METRIC_DYNAMICS: return k == 0 ? 0.0 : v - pv;
-    default: return v;
-  }
-}
-__device__ __forceinline__ void metric_acc(const int metric_id, const bool state_col, const int k, const double w, const double r, const double pr,
-                                           double& a, double& b) {
-  a += r;
-  double x = r;
-  if (metric_id == PK_METRIC_DYNAMICS) x = k == 0 ? 0.0 : r - pr;
-  else if (metric_id == PK_METRIC_VARIANCE && state_col) x = w;
-  b = __builtin_fma(w, x, b);
-}
-// m from the state column's sums (L = T (2 + n_sites) entries), and d m / d theta_p from a tangent column's (a0 = the state column's sum v)
-__device__ __forceinline__ double metric_value(const int metric_id, const double a, const double b, const double c, const double L) {
-  switch (metric_id) {
-    case PK_METRIC_TOTAL_SIGNAL: return a;
-    case PK_METRIC_MEAN_ACTIVITY: return a / L;
-    case PK_METRIC_VARIANCE: { const double ms = a / L - c; return b / L - ms * ms; }      // E[(v-c)^2] - (E[v-c])^2
-    case PK_METRIC_DYNAMICS: return b;
-    default: return sqrt(b);
-  }
-}
-__device__ __forceinline__ double metric_grad(const int metric_id, const double a, const double b, const double a0, const double m, const double c,
-                                              const double L) {
-  switch (metric_id) {
-    case PK_METRIC_TOTAL_SIGNAL: return a;
-    case PK_METRIC_MEAN_ACTIVITY: return a / L;
-    case PK_METRIC_VARIANCE: return (2.0 / L) * __builtin_fma(-(a0 / L - c), a, b);        // (2/L) sum (v - mean) d, from the shifted sums
-    case PK_METRIC_DYNAMICS: return 2.0 * b;
-    default: return m == 0.0 ? 0.0 : b / m;
-  }
-}
 
 // LDS pointers carry their address space explicitly: a pointer that has been through a struct member or a select otherwise degrades to
 // a generic one, and its loads / stores to `flat_*` instructions (measured on the first version of the cube kernels: 7x slower)
@@ -137,10 +39,51 @@ struct Park {            // thread-private LDS slots, slot-major (stride 64: con
   __device__ __forceinline__ void st(int k, double v) const { p[k * 64] = v; }
 };
 
+// The interface sens_kernel uses, for the systems whose two coefficient sets (of theta at 0, of the unit vector e_c at NCOEF) sit in a
+// lane's Park: ChainSys and CubeSys.  D supplies NCOEF, K_A and build / apply / factor / solve / coef_nonfinite on a Park, and holds
+// `Park pk; int S_;` itself: the base is empty, so the size and the member order of D are its own.
+template <class D, int NR>
+struct ParkedSys {
+  __device__ __forceinline__ D& self() { return static_cast<D&>(*this); }
+  __device__ __forceinline__ const D& self() const { return static_cast<const D&>(*this); }
+  static constexpr size_t lds_doubles(int) { return (size_t)2 * D::NCOEF * 64; }
+  __device__ __forceinline__ void init(lds_f64* lds, const int lane, const int, const int c, const double* __restrict__ th, const int n, const int S) {
+    self().pk = Park{lds + lane}; self().S_ = S;
+    D::build(self().pk, 0, [&](int i) { return th[i]; }, 1.0, n);
+    D::build(self().pk, D::NCOEF, [&](int i) { return (i == c - 1) ? 1.0 : 0.0; }, 0.0, n);
+  }
+  __device__ __forceinline__ double cA() const { return self().pk.ld(D::K_A); }
+  __device__ __forceinline__ double dA() const { return self().pk.ld(D::NCOEF + D::K_A); }
+  // Y(ic) = element ic::value of the operand, out(ic, v) receives row ic::value of the product
+  template <class YF, class OF>
+  __device__ __forceinline__ void apply_base(YF&& Y, OF&& out, const double constA) const {
+    double a[NR], f[NR];
+    static_for<NR>([&](auto ic) { a[decltype(ic)::value] = Y(ic); });
+    D::apply(self().pk, 0, 1.0, constA, a, f, self().S_);
+    static_for<NR>([&](auto ic) { out(ic, f[decltype(ic)::value]); });
+  }
+  template <class YF, class OF>
+  __device__ __forceinline__ void apply_deriv(YF&& W, OF&& out, const double constA) const {
+    double a[NR], f[NR];
+    static_for<NR>([&](auto ic) { a[decltype(ic)::value] = W(ic); });
+    D::apply(self().pk, D::NCOEF, 0.0, constA, a, f, self().S_);
+    static_for<NR>([&](auto ic) { out(ic, f[decltype(ic)::value]); });
+  }
+  __device__ __forceinline__ void factor(const double q) { self().factor(self().pk, q, self().S_); }
+  template <class OF>
+  __device__ __forceinline__ void solve(const double (&r)[NR], OF&& out) const {
+    double x[NR];
+    self().solve(r, x, self().S_);
+    static_for<NR>([&](auto ic) { out(ic, x[decltype(ic)::value]); });
+  }
+  __device__ __forceinline__ bool coef_nonfinite() const { return self().coef_nonfinite(self().pk); }
+};
+
 // ---------------------------------------------------------------------------------------------- distributive / successive model
 // rows: 0 = R, 1 = P, 2 + j = site (dist) / level (succ) j.  Coefficients: c1[NR] (coupling to P / to the previous row), dgn[NR] (-diag), cA.
 template <int MODEL, int NS>
-struct ChainSys {
+struct ChainSys : ParkedSys<ChainSys<MODEL, NS>, NS + 2> {
+  using Base = ParkedSys<ChainSys<MODEL, NS>, NS + 2>;
   static_assert(MODEL == M_DIST || MODEL == M_SUCC, "chain systems");
   static constexpr int NR = NS + 2;
   static constexpr int NOBS = NR;                                      // observed rows (i < 2 + n_sites): all of them
@@ -241,46 +184,17 @@ struct ChainSys {
     static_for<NR>([&](auto ic) { constexpr int i = decltype(ic)::value; nf = nf || nonfinite(pk.ld(K_C1 + i)) || nonfinite(pk.ld(K_DG + i)); });
     return nf;
   }
-  // ---- the interface sens_kernel uses
+  // ---- the interface sens_kernel uses: ParkedSys, on these two members
   Park pk; int S_;
-  static constexpr size_t lds_doubles(int) { return (size_t)2 * NCOEF * 64; }
-  __device__ __forceinline__ void init(lds_f64* lds, const int lane, const int, const int c, const double* __restrict__ th, const int n, const int S) {
-    pk = Park{lds + lane}; S_ = S;
-    build(pk, 0, [&](int i) { return th[i]; }, 1.0, n);
-    build(pk, NCOEF, [&](int i) { return (i == c - 1) ? 1.0 : 0.0; }, 0.0, n);
-  }
-  __device__ __forceinline__ double cA() const { return pk.ld(K_A); }
-  __device__ __forceinline__ double dA() const { return pk.ld(NCOEF + K_A); }
-  // Y(ic) = element ic::value of the operand, out(ic, v) receives row ic::value of the product
-  template <class YF, class OF>
-  __device__ __forceinline__ void apply_base(YF&& Y, OF&& out, const double constA) const {
-    double a[NR], f[NR];
-    static_for<NR>([&](auto ic) { a[decltype(ic)::value] = Y(ic); });
-    apply(pk, 0, 1.0, constA, a, f, S_);
-    static_for<NR>([&](auto ic) { out(ic, f[decltype(ic)::value]); });
-  }
-  template <class YF, class OF>
-  __device__ __forceinline__ void apply_deriv(YF&& W, OF&& out, const double constA) const {
-    double a[NR], f[NR];
-    static_for<NR>([&](auto ic) { a[decltype(ic)::value] = W(ic); });
-    apply(pk, NCOEF, 0.0, constA, a, f, S_);
-    static_for<NR>([&](auto ic) { out(ic, f[decltype(ic)::value]); });
-  }
-  __device__ __forceinline__ void factor(const double q) { factor(pk, q, S_); }
-  template <class OF>
-  __device__ __forceinline__ void solve(const double (&r)[NR], OF&& out) const {
-    double x[NR];
-    solve(r, x, S_);
-    static_for<NR>([&](auto ic) { out(ic, x[decltype(ic)::value]); });
-  }
-  __device__ __forceinline__ bool coef_nonfinite() const { return coef_nonfinite(pk); }
+  using Base::factor; using Base::solve; using Base::coef_nonfinite;
 };
 
 // ---------------------------------------------------------------------------------------------- random model, n = NB <= 3 sites
 // rows: 0 = R, 1 + m = bit mask m (m = 0: the unphosphorylated protein).  Coefficients: dg[NM], ci[NM], cA, cB, cC
 // (models/randmod.py:122-247 incl. the lowest-set-bit rate quirk at :201, as in pk_tpr_rand.hpp).
 template <int NB>
-struct CubeSys {
+struct CubeSys : ParkedSys<CubeSys<NB>, (1 << NB) + 1> {
+  using Base = ParkedSys<CubeSys<NB>, (1 << NB) + 1>;
   static constexpr int NM = 1 << NB;
   static constexpr int NR = NM + 1;
   static constexpr int NOBS = 2 + NB;                                   // observed rows: R, P and the masks 1 .. n
@@ -374,39 +288,9 @@ struct CubeSys {
     static_for<NM>([&](auto mc) { constexpr int m = decltype(mc)::value; nf = nf || nonfinite(pk.ld(K_DG + m)) || nonfinite(pk.ld(K_CI + m)); });
     return nf;
   }
-  // ---- the interface sens_kernel uses
+  // ---- the interface sens_kernel uses: ParkedSys, on these two members
   Park pk; int S_;
-  static constexpr size_t lds_doubles(int) { return (size_t)2 * NCOEF * 64; }
-  __device__ __forceinline__ void init(lds_f64* lds, const int lane, const int, const int c, const double* __restrict__ th, const int n, const int S) {
-    pk = Park{lds + lane}; S_ = S;
-    build(pk, 0, [&](int i) { return th[i]; }, 1.0, n);
-    build(pk, NCOEF, [&](int i) { return (i == c - 1) ? 1.0 : 0.0; }, 0.0, n);
-  }
-  __device__ __forceinline__ double cA() const { return pk.ld(K_A); }
-  __device__ __forceinline__ double dA() const { return pk.ld(NCOEF + K_A); }
-  // Y(ic) = element ic::value of the operand, out(ic, v) receives row ic::value of the product
-  template <class YF, class OF>
-  __device__ __forceinline__ void apply_base(YF&& Y, OF&& out, const double constA) const {
-    double a[NR], f[NR];
-    static_for<NR>([&](auto ic) { a[decltype(ic)::value] = Y(ic); });
-    apply(pk, 0, 1.0, constA, a, f, S_);
-    static_for<NR>([&](auto ic) { out(ic, f[decltype(ic)::value]); });
-  }
-  template <class YF, class OF>
-  __device__ __forceinline__ void apply_deriv(YF&& W, OF&& out, const double constA) const {
-    double a[NR], f[NR];
-    static_for<NR>([&](auto ic) { a[decltype(ic)::value] = W(ic); });
-    apply(pk, NCOEF, 0.0, constA, a, f, S_);
-    static_for<NR>([&](auto ic) { out(ic, f[decltype(ic)::value]); });
-  }
-  __device__ __forceinline__ void factor(const double q) { factor(pk, q, S_); }
-  template <class OF>
-  __device__ __forceinline__ void solve(const double (&r)[NR], OF&& out) const {
-    double x[NR];
-    solve(r, x, S_);
-    static_for<NR>([&](auto ic) { out(ic, x[decltype(ic)::value]); });
-  }
-  __device__ __forceinline__ bool coef_nonfinite() const { return coef_nonfinite(pk); }
+  using Base::factor; using Base::solve; using Base::coef_nonfinite;
 };
 
 // ---------------------------------------------------------------------------------------------- random model, n = NB = 4, 5 sites
@@ -622,6 +506,7 @@ template <class Sys, int GP> constexpr size_t sens_metric_lds_bytes(bool dynamic
   return sens_lds_bytes<Sys, GP>() + (dynamics ? ((size_t)(64 / GP) * Sys::NOBS + (size_t)Sys::NOBS * 64) * sizeof(double) : 0);
 }
 
+// The output stage -- index, post-processing, sums, reduction -- is pk_sens_out.hpp's, shared with sens_rows_kernel and rand_sens_kernel.
 // Args = SensArgs, SensMetricArgs for the metric flavour of the output stage (s.metric / dmetric required, s.flat / dflat optional), or
 // SensVjpArgs for the VJP flavour (w / value / grad required, target and s.flat optional)
 template <class Sys, int GP, class Args = SensArgs>
@@ -662,15 +547,15 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const A
   const int T5 = T > 5 ? T - 5 : 0;
   double* const fl = A.flat + rep * F;
   double* const dfl = sens_dflat(SA) + rep * (long long)F * P + (c - 1);
-  // VJP flavour: this column's running sum (the value terms in the base lane, c_f d_fp in a tangent lane), stored once in finish
+  // this column's running sums (sens_accumulate; VJP: sA alone, the value terms in the base lane, c_f d_fp in a tangent lane) and the
+  // metric flavour's shift, in registers; finish stores what they come to, one store per lane.
+  // bpv = the group's post-processed state values at the previous output time, prs = this lane's own entries there -- read by
+  // `dynamics` alone, and only a launch for that metric carries their LDS (sens_metric_lds_bytes): the waves per CU of these kernels are
+  // bounded by LDS at several sizes
   const VjpRow vr = vjp_row(SA, rep, F);
-  double vS = 0.0;
-  // metric flavour: this column's sums (metric_acc) and the shift; bpv = the group's post-processed state values at the previous output
-  // time, prs = this lane's own entries there -- read by `dynamics` alone, and only a launch for that metric carries their LDS
-  // (sens_metric_lds_bytes): the waves per CU of these kernels are bounded by LDS at several sizes
   constexpr int NOBS = Sys::NOBS;
   const bool dyn = MET && A.metric_id == PK_METRIC_DYNAMICS;
-  double mA = 0.0, mB = 0.0, mC = 0.0;
+  double sA = 0.0, sB = 0.0, mC = 0.0;
   lds_f64* const bpv = lds0 + Sys::lds_doubles(NG) + NG * 2 * NR + (CL ? (size_t)2 * NR * 64 : 0) + g * NOBS;
   lds_f64* const prs = lds0 + Sys::lds_doubles(NG) + NG * 2 * NR + (CL ? (size_t)2 * NR * 64 : 0) + NG * NOBS + lane;
   auto emit = [&](const int k, const bool nan_fill) __attribute__((always_inline)) {
@@ -679,55 +564,26 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const A
         double s0 = 0.0;
         static_for<NOBS>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
-          if (i < S && i < 2 + n) s0 += (A.clip && by[i] < 0.0) ? 0.0 : by[i] * (A.normalize ? 1.0 / y0p[i] : 1.0);
+          if (i < S && i < 2 + n) s0 += sens_post_value(A, by[i], A.normalize ? 1.0 / y0p[i] : 1.0, false);
         });
         mC = s0 / (double)(2 + n);
       }
     }
-    static_for<NR>([&](auto ic) {
+    static_for<NOBS>([&](auto ic) {                             // the observed rows i < 2 + n are among the first NOBS
       constexpr int i = decltype(ic)::value;
       if (i < S && i < 2 + n) {
-        const int fi = (i == 0) ? (k >= 5 ? k - 5 : -1) : (i == 1 ? T5 + k : T5 + T + (i - 2) * T + k);
-        if constexpr (VJP) {
-          if (fi >= 0) {                                          // the flat index is the sum index: no slot, no term
-            const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
-            const double qnan = __builtin_nan("");
-            const double v = nan_fill ? qnan : ((A.clip && by[i] < 0.0) ? 0.0 : by[i] * sc);
-            const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
-            double r;
-            if (nan_fill) r = qnan;
-            else r = clipped ? 0.0 : y.template get<i>() * sc;
-            if (is_base && live && A.flat) fl[fi] = r;
-            double term;
-            const double cf = vjp_entry(vr, fi, v, term);        // every lane from the group's published state value
-            vS = is_base ? vS + term : __builtin_fma(cf, r, vS);
-          }
-        } else if constexpr (!MET) {
-          if (fi >= 0 && live) {
-            const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
-            // the value is clipped below 0; its derivative is dropped only where the state is negative beyond the absolute tolerance: a state
-            // that has decayed to +-1e-24 (a rate on the bound 0) is not known to be negative, and its row is what moves the rate off the bound
-            const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
-            double r;
-            if (nan_fill) r = __builtin_nan("");
-            else r = clipped ? 0.0 : y.template get<i>() * sc;
-            if (is_base) fl[fi] = r;
-            else if (is_tan) dfl[(long long)fi * P] = r;
-          }
-        } else if constexpr (i < NOBS) {                        // every observed row enters the sums, the mRNA row at k < 5 (fi < 0) too
+        const int fi = sens_flat_index(i, k, T, T5);
+        // the metric flavour sums every observed row, the mRNA row at k < 5 (fi < 0) too, in every group; the plain flavour only stores
+        if (MET || (fi >= 0 && (VJP || live))) {
           const double sc = A.normalize ? 1.0 / y0p[i] : 1.0;
-          const double qnan = __builtin_nan("");
-          const double v = nan_fill ? qnan : ((A.clip && by[i] < 0.0) ? 0.0 : by[i] * sc);
-          const bool clipped = A.clip && (by[i] < (is_base ? 0.0 : -A.atol));
-          double r;
-          if (nan_fill) r = qnan;
-          else r = clipped ? 0.0 : y.template get<i>() * sc;
+          const double v = sens_post_value(A, by[i], sc, nan_fill);       // every lane from the group's published state value
+          const double r = sens_post_entry(A, by[i], y.template get<i>(), sc, is_base, nan_fill);
           if (fi >= 0 && live) {
-            if (is_base) { if (A.flat) fl[fi] = r; }
-            else if (is_tan && SA.dflat) dfl[(long long)fi * P] = r;
+            if (is_base) { if (sens_writes_flat(SA)) fl[fi] = r; }
+            else if (is_tan && sens_writes_dflat(SA)) dfl[(long long)fi * P] = r;
           }
-          const double w = metric_weight(A.metric_id, k, v, dyn ? (double)bpv[i] : 0.0, mC);
-          metric_acc(A.metric_id, is_base, k, w, r, dyn ? (double)prs[i * 64] : 0.0, mA, mB);
+          const SensRowTerm rt = sens_row_term(SA, vr, fi, k, v, dyn ? (double)bpv[i] : 0.0, mC);
+          sens_accumulate(SA, rt, k, r, is_base, dyn ? (double)prs[i * 64] : 0.0, sA, sB);
           if (dyn) prs[i * 64] = r;
         }
       }
@@ -739,19 +595,13 @@ __global__ __launch_bounds__(64, sens_min_waves<Sys>()) void sens_kernel(const A
     }
   };
   auto finish = [&](const int status, const int acc, const int rej) {
-    if constexpr (VJP) {                                        // in-lane sums: one store per lane
-      if (live) {
-        if (is_base) SA.value[rep] = vr.tg ? 0.5 * vS : vS;
-        else if (is_tan) SA.grad[rep * P + (c - 1)] = vS;
-      }
-    }
-    if constexpr (MET) {                                        // in-lane sums: one store per lane
+    if constexpr (MET || VJP) {                                 // in-lane sums: the base lane's go to every lane of the group
       const double L = (double)T * (double)(2 + n);
-      const double a0 = bcast<GP, 0>(mA), b0 = bcast<GP, 0>(mB);
-      const double m = metric_value(A.metric_id, a0, b0, mC, L);
+      const double a0 = bcast<GP, 0>(sA);
+      const double m = sens_reduce_scalar(SA, vr, a0, bcast<GP, 0>(sB), mC, L);
       if (live) {
-        if (is_base) A.metric[rep] = m;
-        else if (is_tan) SA.dmetric[rep * P + (c - 1)] = metric_grad(A.metric_id, mA, mB, a0, m, mC, L);
+        if (is_base) sens_scalar(SA)[rep] = m;
+        else if (is_tan) sens_grad(SA)[rep * P + (c - 1)] = sens_reduce_grad(SA, sA, sB, a0, m, mC, L);
       }
     }
     if (is_base && live) {

@@ -44,7 +44,7 @@ __device__ __forceinline__ void row_coef_deriv(const int p, const int n, const i
   }
 }
 
-// Args = SensArgs, or SensMetricArgs / SensVjpArgs (pk_sens.hpp) for the metric / VJP flavour of the output stage
+// Args = SensArgs, or SensMetricArgs / SensVjpArgs for the metric / VJP flavour of the output stage (pk_sens_out.hpp)
 template <int MODEL, int G, int KC, class Args = SensArgs>
 __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
   constexpr bool MET = sens_metric_flavour<Args>(), VJP = sens_vjp_flavour<Args>();
@@ -81,79 +81,55 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
   const double yscale = (A.normalize && row < S) ? 1.0 / y_init : 1.0;
   double* const fl = A.flat + rep * F;
   double* const dfl = sens_dflat(SA) + rep * (long long)F * P + (long long)ch * KT;
-  // metric flavour: the sums of this lane's row for the state column (index 0) and its KT tangents and the row's entries at the previous
-  // output time live in thread-private LDS slots (3 KC per thread, touched only at the output times: the step loop keeps its registers
-  // and its two waves per SIMD); mC = the shift
+  // metric / VJP flavour: the running sums of this lane's row (sens_accumulate) for the state column (index 0) and its KT tangents live in
+  // thread-private LDS slots, touched only at the output times: the step loop keeps its registers and its two waves per SIMD.  The VJP
+  // flavour carries slotA alone (KC per thread); the metric flavour slotB and the row's entries at the previous output time as well
+  // (3 KC per thread); mC = its shift.  A chunk forms the VJP's c_f from its own state column
+  constexpr int NSUM = sens_sum_count<Args>();
   extern __shared__ __align__(16) double sens_rows_lds[];
   lds_f64* const ms = (lds_f64*)sens_rows_lds + threadIdx.x;
   auto slotA = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[k * 256]; };
   auto slotB = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[(KC + k) * 256]; };
   auto slotP = [&](const int k) __attribute__((always_inline)) -> lds_f64& { return ms[(2 * KC + k) * 256]; };
   double mC = 0.0;
-  if constexpr (MET) static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = 0.0; slotB(k) = 0.0; slotP(k) = 0.0; });
-  // VJP flavour: the running sums of this lane's row -- the value terms (index 0) and c_f d_fp of its KT tangents -- in the first KC of the
-  // same slots (KC per thread); a chunk forms c_f from its own state column
+  static_for<KC>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
+    if constexpr (NSUM >= 1) slotA(k) = 0.0;
+    if constexpr (MET) { slotB(k) = 0.0; slotP(k) = 0.0; }
+  });
   const VjpRow vr = vjp_row(SA, rep, F);
-  if constexpr (VJP) static_for<KC>([&](auto kc) { slotA(decltype(kc)::value) = 0.0; });
   auto emit = [&](const int kk, const bool nan_fill) {
-    if constexpr (VJP) {                                   // the flat index is the sum index: no slot, no term
-      if (!observed) return;
-      const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
-      if (fi < 0) return;
-      const bool clipped = A.clip && (y[0] < 0.0);
-      const bool dropped = A.clip && (y[0] < -A.atol);
-      const double qnan = __builtin_nan("");
-      const double v = nan_fill ? qnan : (clipped ? 0.0 : y[0] * yscale);
-      if (ch == 0 && A.flat) fl[fi] = v;
-      double term;
-      const double cf = vjp_entry(vr, fi, v, term);
-      double sa[KC];                                         // all slots first: their latencies overlap
-      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; sa[k] = slotA(k); });
-      sa[0] += term;
-      static_for<KT>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const double d = nan_fill ? qnan : (dropped ? 0.0 : y[1 + k] * yscale);
-        sa[1 + k] = __builtin_fma(cf, d, sa[1 + k]);
-      });
-      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = sa[k]; });
-      return;
-    }
-    if constexpr (MET) {                                   // every observed row enters the sums, the mRNA row at kk < 5 (fi < 0) too
-      const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
-      const bool clipped = A.clip && (y[0] < 0.0);
-      const bool dropped = A.clip && (y[0] < -A.atol);
-      const double qnan = __builtin_nan("");
-      const double v = nan_fill ? qnan : (clipped ? 0.0 : y[0] * yscale);
+    const int fi = sens_flat_index(row, kk, T, T5);
+    // the metric flavour sums every observed row, the mRNA row at kk < 5 (fi < 0) too, and its shift needs the whole group
+    if (!MET && (!observed || fi < 0)) return;
+    const double v = sens_post_value(A, y[0], yscale, nan_fill);
+    if constexpr (MET) {
       if (kk == 0) mC = gsum<G>(observed ? v : 0.0, lane) / (double)(2 + n);       // called once, before the step loop: the whole group is here
       if (!observed) return;
-      if (fi >= 0 && ch == 0 && A.flat) fl[fi] = v;
-      const bool dyn = A.metric_id == PK_METRIC_DYNAMICS;      // the only metric that reads the previous output time's entries
-      const double pv = dyn ? (double)slotP(0) : 0.0;
-      const double w = metric_weight(A.metric_id, kk, v, pv, mC);
-      double sa[KC], sb[KC];                                 // all slots first: their latencies overlap
-      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; sa[k] = slotA(k); sb[k] = slotB(k); });
-      static_for<KT>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const double d = nan_fill ? qnan : (dropped ? 0.0 : y[1 + k] * yscale);
-        if (fi >= 0 && SA.dflat && ch * KT + k < P) dfl[(long long)fi * P + k] = d;
-        metric_acc(A.metric_id, false, kk, w, d, dyn ? (double)slotP(1 + k) : 0.0, sa[1 + k], sb[1 + k]);
-        if (dyn) slotP(1 + k) = d;
-      });
-      metric_acc(A.metric_id, true, kk, w, v, pv, sa[0], sb[0]);
-      if (dyn) slotP(0) = v;
-      static_for<KC>([&](auto kc) { constexpr int k = decltype(kc)::value; slotA(k) = sa[k]; slotB(k) = sb[k]; });
-      return;
     }
-    if (!observed) return;
-    const int fi = (row == 0) ? (kk >= 5 ? kk - 5 : -1) : (row == 1 ? T5 + kk : T5 + T + (row - 2) * T + kk);
-    if (fi < 0) return;
-    const bool clipped = A.clip && (y[0] < 0.0);
-    const bool dropped = A.clip && (y[0] < -A.atol);       // derivative rows: negative beyond the absolute tolerance (pk_sens.hpp, emit)
-    const double qnan = __builtin_nan("");
-    if (ch == 0) fl[fi] = nan_fill ? qnan : (clipped ? 0.0 : y[0] * yscale);
+    if (fi >= 0 && ch == 0 && sens_writes_flat(SA)) fl[fi] = v;
+    const bool dyn = MET && A.metric_id == PK_METRIC_DYNAMICS;      // the only metric that reads the previous output time's entries
+    const double pv = dyn ? (double)slotP(0) : 0.0;
+    const SensRowTerm rt = sens_row_term(SA, vr, fi, kk, v, pv, mC);
+    double sa[KC], sb[KC];                                   // all slots first: their latencies overlap
+    static_for<KC>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      if constexpr (NSUM >= 1) sa[k] = slotA(k);
+      if constexpr (NSUM == 2) sb[k] = slotB(k);
+    });
     static_for<KT>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
-      if (ch * KT + k < P) dfl[(long long)fi * P + k] = nan_fill ? qnan : (dropped ? 0.0 : y[1 + k] * yscale);
+      const double d = sens_post_entry(A, y[0], y[1 + k], yscale, false, nan_fill);
+      if (fi >= 0 && sens_writes_dflat(SA) && ch * KT + k < P) dfl[(long long)fi * P + k] = d;
+      sens_accumulate(SA, rt, kk, d, false, dyn ? (double)slotP(1 + k) : 0.0, sa[1 + k], sb[1 + k]);
+      if (dyn) slotP(1 + k) = d;
+    });
+    sens_accumulate(SA, rt, kk, v, true, pv, sa[0], sb[0]);
+    if (dyn) slotP(0) = v;
+    static_for<KC>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      if constexpr (NSUM >= 1) slotA(k) = sa[k];
+      if constexpr (NSUM == 2) slotB(k) = sb[k];
     });
   };
   auto fail_from = [&](int kk) {
@@ -161,25 +137,16 @@ __global__ __launch_bounds__(256) void sens_rows_kernel(const Args SA) {
     for (; kk < T; ++kk) emit(kk, true);
   };
   auto finish = [&](const int status, const int acc, const int rej) {
-    if constexpr (VJP) {                                   // across the G lanes of the group, column by column (rows beyond the observed ones hold zeros)
-      const double v0 = gsum<G>(slotA(0), lane);
-      static_for<KT>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const double gk = gsum<G>(slotA(1 + k), lane);
-        if (row == 0 && ch * KT + k < P) SA.grad[rep * P + ch * KT + k] = gk;
-      });
-      if (row == 0 && ch == 0) SA.value[rep] = vr.tg ? 0.5 * v0 : v0;
-    }
-    if constexpr (MET) {                                   // across the G lanes of the group, column by column (rows beyond the observed ones hold zeros)
+    if constexpr (NSUM >= 1) {                             // across the G lanes of the group, column by column (rows beyond the observed ones hold zeros)
       const double L = (double)T * (double)(2 + n);
-      const double a0 = gsum<G>(slotA(0), lane), b0 = gsum<G>(slotB(0), lane);
-      const double m = metric_value(A.metric_id, a0, b0, mC, L);
+      const double a0 = gsum<G>(slotA(0), lane), b0 = NSUM == 2 ? gsum<G>(slotB(0), lane) : 0.0;
+      const double m = sens_reduce_scalar(SA, vr, a0, b0, mC, L);
       static_for<KT>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        const double a = gsum<G>(slotA(1 + k), lane), b = gsum<G>(slotB(1 + k), lane);
-        if (row == 0 && ch * KT + k < P) SA.dmetric[rep * P + ch * KT + k] = metric_grad(A.metric_id, a, b, a0, m, mC, L);
+        const double a = gsum<G>(slotA(1 + k), lane), b = NSUM == 2 ? gsum<G>(slotB(1 + k), lane) : 0.0;
+        if (row == 0 && ch * KT + k < P) sens_grad(SA)[rep * P + ch * KT + k] = sens_reduce_grad(SA, a, b, a0, m, mC, L);
       });
-      if (row == 0 && ch == 0) A.metric[rep] = m;
+      if (row == 0 && ch == 0) sens_scalar(SA)[rep] = m;
     }
     if (row != 0) return;
     if (A.status && status) atomicOr(&A.status[rep], status);          // zeroed by the launcher: a failure in ANY chunk flags the replica

@@ -38,7 +38,7 @@ def _oracle_jac(model, th, y0, n, t):
     return np.stack(cols, axis=1)                      # [F, P]
 
 
-CASES = [# column-per-lane kernel (csrc/pk_sens.hpp): the default below distmod n = 10 / succmod n = 6 (launch_sens, pk_inst_sens_rand.hip)
+CASES = [# column-per-lane kernel (csrc/pk_sens.hpp): the default below distmod n = 10 / succmod n = 6 (launch_sens_any, pk_inst_sens.inc)
          ("distmod", 1), ("distmod", 3), ("distmod", 4), ("distmod", 8), ("succmod", 1), ("succmod", 2), ("succmod", 5),
          # rows-per-lane kernel (csrc/pk_sens_rows.hpp) in 16-lane groups (S <= 16), the default from distmod n = 10 / succmod n = 6 on; the
          # column kernel at these sizes (PK_SENS_ROWS=2) and the rows kernel below them (=1): tests/test_gpu_sens_regimes.py, forced kernels

@@ -20,7 +20,7 @@ Measured on an MI355X (worst over the sizes of a family and replicas 0, B - 1; p
     steady start 2.7e-12; forced kernels 4.4e-12; t up to 1e5 3.5e-10, intervals down to 1e-6 8.8e-16.
   default tolerances, tangent band error max |d - d_ref| / (1e-8 + 1e-6 |d_ref|), limit 1: U(0, 20) 4.0e-3, log-uniform 0.14 (succmod
     30), zeros 2.3e-2, steady start 2.4e-3 -- the states of the same runs: 1.8e-2, 1.6e-2, 1.1e-2, 1.6e-8.  No family exceeds the band.
-  Before the derivative rows of states within atol of 0 were kept (csrc/pk_sens.hpp, emit), the zeros regime missed both limits in every
+  Before the derivative rows of states within atol of 0 were kept (csrc/pk_sens_out.hpp, sens_post_entry), the zeros regime missed both limits in every
   family: 0.01 .. 1.0 in the first metric, 1e6 band units (a row of zeros against a derivative of order 1).
 """
 import functools
