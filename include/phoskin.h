@@ -240,6 +240,11 @@ int pk_solve_protein_sens_vjp_batch(pk_ctx*, int model, int n_sites, int64_t B,
  *   weighted residuals at each row's last Jacobian evaluation (what a covariance needs); reason [R] | NULL why the row stopped: 0 ftol / xtol,
  *   1 gradient / empty free set, 2 damping budget, 3 max_iter.  All of these are DEVICE pointers; counters is a HOST array:
  *   {iterations, solves, launches, host waits, Jacobian phases, trial rounds}.
+ *   JTJ belongs to the point the row's last Jacobian phase was taken AT, which is the point BEFORE that iteration's step: a row that stops
+ *   in its first iteration (for any reason, max_iter = 1 included) holds J^T J at clip(P0), not at the p it returns, and in general JTJ is
+ *   one accepted step behind p unless the row's last iteration took no step (reasons 1 and 2).  With max_iter = 0 no
+ *   Jacobian phase runs: JTJ is NOT WRITTEN and the caller's buffer keeps what it held; p = clip(P0), r and cost are the start point's,
+ *   reason = 3 and counters = {0, R, 1, 0, 0, 0}.
  * Every iteration is a Jacobian phase (gather, pk_solve_protein_sens_batch on the active rows, normal equations: 3 launches, in row chunks
  * where the Jacobians of a launch would pass 1 GiB) and trial rounds (damped steps, pk_solve_protein_batch on levels x pending rows, accept
  * rule: 3 launches); the host waits once per phase and once per round, for one flag per row, and nothing else crosses PCIe but the row
