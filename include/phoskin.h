@@ -461,6 +461,34 @@ int pk_network_simulate_measure_batch(pk_ctx*, pk_net*, pk_loss* lists, int64_t 
                                       int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, double eps, int metric_id,
                                       double* Y, double* pred, double* metric, int32_t* status, int32_t* n_steps);
 
+/* Y(t) AND dY / dx_c for K chosen entries c = cols[k] of the candidate vector from ONE integration (forward sensitivities: the augmented
+ * system s_c' = f_y s_c + df / dx_c, s_c(t0) = 0 -- y0 is data --, integrated with the state by the order-3 Rosenbrock-W method; every
+ * tangent stage is solved with the state's per-protein block factors of that step and its right-hand side is the exact directional
+ * derivative of the network right-hand side: csrc/pk_network_sens.hpp).  Replaces differencing pk_network_simulate_batch by hand.
+ *   cols [K] HOST pointer: indices into x in its own order [c_k | A | B | C | D | Dp | E | tf_scale]; an index outside [0, n_var) or a
+ *   repeated one is PK_ERR_ARG.  dY [B,T,S,K], the K derivatives of one state at one time contiguous; row t = 0 of dY is 0.  Y [B,T,S] | NULL.
+ *   With x_is_raw the derivative is with respect to the RAW entry: the physical derivative times softplus'(raw), exactly 1 where softplus
+ *   returns its argument (raw > 20).  x, y0, Y, dY, status, n_steps: DEVICE pointers; t, cols: HOST.
+ * Always PK_METHOD_ROS34PW2 on the general LDS kernel, whatever opts->method / linsolve say -- except that an explicit PK_METHOD_ARK436,
+ * PK_METHOD_DP5 or PK_KERNEL_WORKSPACE is PK_ERR_UNSUPPORTED (pk_last_error names the remedy), as is a network on which not one column
+ * fits beside the state in 160 KiB of LDS or that is beyond the LDS kernel (S > 1024, N > 512): the workspace kernel carries no tangents.
+ * Tangents are held to the same rtol / atol as the states, in the norm opts->err_norm selects (maximum over states and columns; RMS: over
+ * all S (1 + columns of the workgroup) entries).
+ * Column chunks: one workgroup integrates one candidate with up to KC = pk_network_sens_columns_per_launch columns, the launch is
+ * B x ceil(K / KC) workgroups.  Every chunk integrates the state itself with its own step-size control: each column is within rtol / atol
+ * of the exact derivative, the chunks are not bit-coupled.  Chunk 0 writes Y; status is the OR over the chunks; n_steps is chunk 0's.
+ * Failure: a flagged chunk leaves NaN in its own columns at the rows it did not reach, and in every row when it is PK_ST_NONFINITE (a
+ * non-finite state, parameter or tangent, or a tangent beyond 1e100 in magnitude, at a step whose error is not finite); Y follows
+ * pk_network_simulate_batch's rule.
+ * K = 0 with Y set is pk_network_simulate_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED, bit for bit; B = 0 is PK_OK; dY NULL
+ * with K > 0 is PK_ERR_ARG.  A candidate's results do not depend on the batch around it. */
+int pk_network_simulate_sens_batch(pk_ctx*, pk_net*, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
+                                   const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host, int K,
+                                   double* Y, double* dY, int32_t* status, int32_t* n_steps);
+/* KC of pk_network_simulate_sens_batch on this network: the largest column count whose LDS request stays within 160 KiB (at most n_var);
+ * 0 = not one column fits.  Pure host arithmetic. */
+int pk_network_sens_columns_per_launch(pk_net*);
+
 /* Timing hook for bench.py: runs `iters` back-to-back launches of pk_solve_protein_batch on the context's
  * stream between two hipEvents and returns the mean kernel time per launch in milliseconds (< 0 on error). */
 double pk_time_solve_protein_batch(pk_ctx*, int iters, int model, int n_sites, int64_t B,

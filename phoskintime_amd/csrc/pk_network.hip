@@ -10,6 +10,7 @@
 #include "pk_network_solve_reg.hpp"
 #include "pk_network_solve_reg2.hpp"
 #include "pk_network_rk45.hpp"
+#include "pk_network_sens.hpp"
 namespace pk {
 // persistent grid: min(B, workgroups of `kernel` at `threads` each resident on the current device at once)
 hipError_t net_persistent_grid(const void* kernel, int threads, long long B, int* grid);
@@ -24,6 +25,8 @@ hipError_t launch_net_lds_fused(const NetDev& n, const NetSolveArgs& a, long lon
 hipError_t net_ws_measure_grid(const NetDev& n, long long B, int* grid);
 hipError_t launch_net_ws_measure(const NetDev& n, const NetSolveArgs& a, long long B, int grid, double* ws, hipStream_t st);
 hipError_t launch_net_lds_measure(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st);
+// ... and carrying forward parameter sensitivities, one workgroup per (candidate, column chunk) (pk_inst_net_rosw_sens.hip)
+hipError_t launch_net_lds_sens(const NetDev& n, const NetSolveArgs& a, const NetSensArgs& s, long long B, int threads, size_t lds, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
@@ -362,19 +365,24 @@ int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { ret
 // `fused`: null, or the loss fields of NetSolveArgs filled in (pk_network_simulate_objective_batch); Y may then be null.  With
 // fused->loss_ptr set (the time-bucketed lists: the caller asked for the order-3 method or the workspace kernel) the launch runs where the
 // plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel.  fused->meas: the same lists measured
-// instead of scored (pk_network_simulate_measure_batch), on the same two kernels
+// instead of scored (pk_network_simulate_measure_batch), on the same two kernels.  `sens`: null, or the columns of
+// pk_network_simulate_sens_batch (cols: HOST pointer; Y may then be null): the plan must be the general LDS kernel
+struct NetSensReq { const int32_t* cols_host; int K, KC; double* dY; };
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                              const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps,
-                             const pk::NetSolveArgs* fused) {
+                             const pk::NetSolveArgs* fused, const NetSensReq* sens = nullptr) {
   if (!c || !n) return PK_ERR_ARG;
   if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
   if (T < 1 || !t_host) return pk_ctx_fail(c, PK_ERR_ARG, "t must hold >= 1 time points (host pointer)");
   if (B == 0) return PK_OK;
-  if (!x || !y0 || (!Y && !fused)) return pk_ctx_fail(c, PK_ERR_ARG, "null pointer");
+  if (!x || !y0 || (!Y && !fused && !sens)) return pk_ctx_fail(c, PK_ERR_ARG, "null pointer");
   if (B > 0x7fffffffLL) return pk_ctx_fail(c, PK_ERR_ARG, "batch too large for one launch");
   if (n->d.model == 2 && n->max_sites > 16) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "combinatorial topology: <= 16 sites per protein");
   NetPlan plan = net_plan(n, opts_in);
   if (plan.code != PK_OK) return pk_ctx_fail(c, plan.code, plan.refusal);
+  if (sens && plan.kernel != NetKernel::Lds)
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: the general LDS kernel only (S <= 1024, N <= 512, 160 KiB of LDS); the "
+                                              "HBM-workspace kernel carries no tangents: difference pk_network_simulate_batch there");
   const bool rosw_fused = fused && fused->loss_ptr;
   const bool measure = rosw_fused && fused->meas;
   if (measure) {
@@ -532,6 +540,22 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       // every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
       int threads = (n->d.S <= 128 && n->d.N <= 64) ? 64 : 256;        // measured at S = 500: 256 threads beat 128 by 1.33x
       if (const char* e = getenv("PK_NET_THREADS")) { const int v = atoi(e); if ((v == 64 || v == 128 || v == 256) && n->d.S <= 4 * v && n->d.N <= 2 * v) threads = v; }
+      if (sens) {
+        // B x ceil(K / KC) workgroups; the column indices go through the context's scratch arena; status is OR-ed over the chunks
+        const int kcl = std::min(sens->K, sens->KC);
+        if ((size_t)kcl * n->d.S > 512) threads = 256;
+        struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; const NetSensReq* s; long long B; int threads; size_t lds; int32_t* status; }
+            q{&n->d, &a, sens, (long long)B, threads, pk::net_sens_lds_bytes(n->d, n->nnzT, kcl), status};
+        auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
+          const Q& r = *(const Q*)user;
+          hipError_t e = hipMemcpyAsync(scratch, r.s->cols_host, (size_t)r.s->K * sizeof(int32_t), hipMemcpyHostToDevice, s);
+          if (e == hipSuccess && r.status) e = hipMemsetAsync(r.status, 0, (size_t)r.B * sizeof(int32_t), s);
+          if (e != hipSuccess) return e;
+          const pk::NetSensArgs sa{(const int32_t*)scratch, r.s->K, r.s->KC, r.s->dY};
+          return pk::launch_net_lds_sens(*r.d, *r.a, sa, r.B, r.threads, r.lds, s);
+        };
+        return pk_ctx_scratch_launch(c, (size_t)sens->K * sizeof(int32_t), launch, &q);
+      }
       if (rosw_fused) {
         const size_t lb = pk::net_solve_fused_lds_bytes(n->d, n->nnzT);
         const hipError_t ef = measure ? pk::launch_net_lds_measure(n->d, a, (long long)B, threads, lb, stream)
@@ -621,6 +645,54 @@ int pk_network_simulate_measure_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_t 
   if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the index lists were created for");
   f.meas = 1; f.meas_id = metric_id; f.meas_eps = eps; f.meas_pred = pred; f.meas_metric = metric;
   return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps, &f);
+}
+
+// Columns one workgroup of the sensitivity kernel carries on this network: the largest count whose LDS request (net_sens_lds_bytes) stays
+// within 160 KiB, at most n_var; 0 where not even one fits or the network is beyond the LDS kernel's thread layout.  Host arithmetic only
+// (dev knob PK_NET_SENS_KC: a smaller count, read at every call)
+int pk_network_sens_columns_per_launch(pk_net* n) {
+  if (!n) return PK_ERR_ARG;
+  if (n->d.S > 1024 || n->d.N > 512) return 0;
+  int kc = std::min(pk::net_sens_max_columns(n->d, n->nnzT, 160 * 1024), n->d.n_var);
+  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < kc) kc = v; }
+  return kc;
+}
+
+// Y and dY / dx[cols] from one integration of the augmented system (pk_network_sens.hpp).  Always the order-3 method on the general LDS
+// kernel; K = 0 is pk_network_simulate_batch on that kernel
+int pk_network_simulate_sens_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
+                                   const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host, int K, double* Y,
+                                   double* dY, int32_t* status, int32_t* n_steps) {
+  if (!c || !n) return PK_ERR_ARG;
+  if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
+  if (K < 0) return pk_ctx_fail(c, PK_ERR_ARG, "K must be >= 0");
+  if (opts && (opts->method == PK_METHOD_ARK436 || opts->method == PK_METHOD_DP5))
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities integrate with PK_METHOD_ROS34PW2 only: leave opts->method at its default or ask for "
+                                              "PK_METHOD_ROS34PW2");
+  if (opts && opts->kernel == PK_KERNEL_WORKSPACE)
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities run on the general LDS kernel only: leave opts->kernel at PK_KERNEL_AUTO");
+  if (K > 0) {
+    if (!cols_host) return pk_ctx_fail(c, PK_ERR_ARG, "cols is NULL with K > 0");
+    if (!dY) return pk_ctx_fail(c, PK_ERR_ARG, "dY is NULL with K > 0");
+    std::vector<char> seen((size_t)n->d.n_var, 0);
+    for (int k = 0; k < K; ++k) {
+      const int col = cols_host[k];
+      if (col < 0 || col >= n->d.n_var) return pk_ctx_fail(c, PK_ERR_ARG, "cols: index outside [0, n_var)");
+      if (seen[col]) return pk_ctx_fail(c, PK_ERR_ARG, "cols: an index is repeated");
+      seen[col] = 1;
+    }
+  } else if (!Y && B > 0) return pk_ctx_fail(c, PK_ERR_ARG, "K = 0 and Y is NULL: nothing to compute");
+  if (B == 0) return PK_OK;
+  pk_solver_opts o;
+  if (opts) o = *opts; else pk_default_opts(&o);
+  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = PK_KERNEL_AUTO;
+  if (K == 0) return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr);
+  const int KC = pk_network_sens_columns_per_launch(n);
+  if (KC < 1)
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: not one tangent column fits beside the state in one workgroup's LDS (160 KiB) on this "
+                                              "network, or it is beyond the LDS kernel (S <= 1024, N <= 512); difference pk_network_simulate_batch");
+  const NetSensReq req{cols_host, K, KC, dY};
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr, &req);
 }
 
 int pk_network_unpack_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x_raw, double* x_phys) {

@@ -304,6 +304,64 @@ class NetworkEngine:
         val._keepalive = (xd, yd)  # type: ignore[attr-defined]
         return val, pred, status, nsteps, Y
 
+    def sens_columns_per_launch(self) -> int:
+        """Tangent columns one workgroup of ``simulate_sens_batch`` carries on this network (``pk_network_sens_columns_per_launch``: host
+        arithmetic on the LDS budget); 0 when not even one fits."""
+        return int(_capi.load().pk_network_sens_columns_per_launch(self._h))
+
+    def simulate_sens_batch(self, x, t_eval, cols, y0=None, raw: bool = False, rtol: Optional[float] = None, atol: Optional[float] = None,
+                            max_steps: int = 1000000, want_Y: bool = True, method: str = "auto", kernel: str = "auto", err_norm: str = "max"):
+        """The trajectory AND its derivative with respect to the entries ``cols`` of the candidate vector (indices into ``x``, in
+        ``pack_params`` order) from ONE integration: forward sensitivities on the order-3 Rosenbrock-W integrator
+        (``pk_network_simulate_sens_batch``, csrc/pk_network_sens.hpp).  Returns (dY [B, T, S, K], Y [B, T, S] or None, status [B],
+        n_steps [B, 2]) as GPU tensors; ``dY[:, 0]`` is 0 (``y0`` is data).  ``raw=True``: ``x`` holds raw entries and the derivative is
+        with respect to them (physical derivative times softplus').  Default tolerances are the order-3 kernel's, 1e-7 / 1e-9, as in
+        ``simulate_measure_batch``; tangents are held to the same tolerances as the states.  The launch always runs the order-3 method on
+        the general LDS kernel, ``sens_columns_per_launch()`` columns per workgroup, each chunk of columns integrating the state itself:
+        ``status`` is the OR over the chunks, ``n_steps`` is chunk 0's.  A flagged candidate has NaN in the columns of the flagged chunk
+        at the rows it did not reach.  ``None`` when the launch is refused (PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy):
+        ``method`` "ark" / "dp5", ``kernel="workspace"``, or a network on which no column fits in one workgroup's LDS.  This is a tool for
+        the local sensitivity of a chosen handful of parameters -- per column about (1 + KC) / KC state integrations against 2 for central
+        differences --, not a full gradient."""
+        if method not in ("auto", "ark", "rosw", "dp5"):
+            raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
+        if kernel not in ("auto", "lds", "workspace"):
+            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
+        rtol = 1e-7 if rtol is None else rtol
+        atol = 1e-9 if atol is None else atol
+        dev = torch.device("cuda", self.ctx.device)
+        xd = _dev_f64(x, dev)
+        if xd.dim() == 1:
+            xd = xd.unsqueeze(0)
+        if xd.shape[1] != self.n_var:
+            raise ValueError(f"x must be [B, {self.n_var}]")
+        B = xd.shape[0]
+        yd = _dev_f64(self.default_y0() if y0 is None else y0, dev)
+        if yd.shape == (self.S,):
+            yb = 0
+        elif yd.shape == (B, self.S):
+            yb = 1
+        else:
+            raise ValueError(f"y0 must be [{self.S}] or [{B}, {self.S}]")
+        th = np.ascontiguousarray(np.atleast_1d(np.asarray(t_eval, dtype=np.float64)))
+        T = th.size
+        ch = _i32(np.atleast_1d(cols)).reshape(-1)
+        K = int(ch.size)
+        Y = torch.empty((B, T, self.S), dtype=torch.float64, device=dev) if want_Y else None
+        dY = torch.empty((B, T, self.S, K), dtype=torch.float64, device=dev)
+        status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        nsteps = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+        opts = self._opts(method, kernel, rtol=rtol, atol=atol, max_steps=max_steps, err_norm=err_norm)
+        self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self.ctx.lib.pk_network_simulate_sens_batch(self.ctx.handle, self._h, B, _ptr(xd), int(raw), _ptr(yd), yb, th.ctypes.data, T,
+                                                         C.byref(opts), ch.ctypes.data if K else None, K, _ptr(Y), _ptr(dY) if K else None,
+                                                         _ptr(status), _ptr(nsteps))
+        if rc == _capi.PK_ERR_UNSUPPORTED:
+            return None
+        self.ctx.check(rc)
+        dY._keepalive = (xd, yd, ch)  # type: ignore[attr-defined]
+        return dY, Y, status, nsteps
+
     def resolved_method(self, method: str = "auto", kernel: str = "auto") -> str:
         """The integrator ``simulate_batch(method=, kernel=)`` will run on this network -- "ark", "rosw" or "dp5" -- as decided by the
         library itself (``pk_network_resolve_method``: network size, sites per protein AND the LDS footprint of the order-4 kernel).

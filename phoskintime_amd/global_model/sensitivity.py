@@ -186,6 +186,112 @@ def run_sensitivity_batch(eng: NetworkEngine, fitted_params: Dict, times_p, time
     return out
 
 
+_METRICS = ("total_signal", "mean", "variance", "l2_norm")
+
+
+def observable_weights(eng: NetworkEngine, ld: dict) -> np.ndarray:
+    """W [n_obs, S] with pred's numerator = W @ Y[t] and baseline = W @ Y[base], rows in (protein | rna | phospho) order of the index
+    lists ``ld`` (``make_index_lists``): the total protein (P plus all sites / all 2^ns states), the mRNA row, a site's row (combinatorial
+    topology: all masks with the site's bit)."""
+    oy, ns, comb = eng._keep[0], eng._keep[2], eng.model == 2
+    n_obs = ld["p_prot"].size + ld["p_rna"].size + ld["p_pho"].size
+    W = np.zeros((n_obs, eng.S))
+    r = 0
+    for i in ld["p_prot"]:
+        cnt = (1 << int(ns[i])) if comb else 1 + int(ns[i])
+        W[r, oy[i] + 1: oy[i] + 1 + cnt] = 1.0; r += 1
+    for i in ld["p_rna"]:
+        W[r, oy[i]] = 1.0; r += 1
+    for i, j in zip(ld["p_pho"], ld["s_pho"]):
+        if comb:
+            m = np.arange(1 << int(ns[i]))
+            W[r, oy[i] + 1 + m[(m >> int(j)) & 1 == 1]] = 1.0
+        else:
+            W[r, oy[i] + 2 + int(j)] = 1.0
+        r += 1
+    return W
+
+
+def fold_change_derivatives(W: np.ndarray, ld: dict, Y: np.ndarray, dY: np.ndarray, eps: float = 1e-12):
+    """(pred [n_obs], dpred [n_obs, K]) of one trajectory Y [T, S] with tangents dY [T, S, K]: pred = max(a, eps) / max(c, eps) with
+    numerator a at the entry's time and baseline c at its modality's baseline index, differentiated through both; a floor that is active
+    has derivative 0."""
+    t_idx = np.concatenate([ld["t_prot"], ld["t_rna"], ld["t_pho"]]).astype(np.int64)
+    b_idx = np.concatenate([np.full(ld["p_prot"].size, int(ld["prot_base_idx"])), np.full(ld["p_rna"].size, int(ld["rna_base_idx"])),
+                            np.full(ld["p_pho"].size, int(ld["pho_base_idx"]))]).astype(np.int64)
+    a = np.einsum("os,os->o", W, Y[t_idx]); c = np.einsum("os,os->o", W, Y[b_idx])
+    da = np.einsum("os,osk->ok", W, dY[t_idx]); dc = np.einsum("os,osk->ok", W, dY[b_idx])
+    am, cm = np.maximum(a, eps), np.maximum(c, eps)
+    da = np.where((a > eps)[:, None], da, 0.0); dc = np.where((c > eps)[:, None], dc, 0.0)
+    return am / cm, da / cm[:, None] - (am / (cm * cm))[:, None] * dc
+
+
+def metric_derivatives(pred: np.ndarray, dpred: np.ndarray) -> Dict:
+    """{metric: (value, gradient [K])} of the four ``_compute_scalar_metric`` outputs over pred [n_obs] with d pred [n_obs, K]: sum;
+    sum / n; (2 / n) sum (p - mean) dp; sum p dp / |p| (0 where |p| = 0).  Empty lists give 0."""
+    n, K = pred.size, dpred.shape[1]
+    if n == 0:
+        return {m: (0.0, np.zeros(K)) for m in _METRICS}
+    mu, nrm = float(np.mean(pred)), float(np.linalg.norm(pred))
+    return {"total_signal": (float(np.sum(pred)), dpred.sum(axis=0)), "mean": (mu, dpred.sum(axis=0) / n),
+            "variance": (float(np.var(pred)), (2.0 / n) * ((pred - mu) @ dpred)),
+            "l2_norm": (nrm, (pred @ dpred) / nrm if nrm > 0.0 else np.zeros(K))}
+
+
+def local_sensitivity_batch(eng: NetworkEngine, params: Dict, t_prot, t_rna, t_pho, vary=None, metric: str = config.SENSITIVITY_METRIC,
+                            perturbation: float = config.SENSITIVITY_PERTURBATION, y0=None, rtol: Optional[float] = None,
+                            atol: Optional[float] = None, eps: float = 1e-12, max_steps: int = 1000000) -> Dict:
+    """Local sensitivities of the network's fold-change observables and of the Morris output at ``params`` (the eight parameter groups,
+    as ``run_sensitivity_batch`` takes them) from ONE ``simulate_sens_batch`` launch -- exact tangents of the discrete solution, where
+    differencing ``simulate_batch`` takes two solves per entry and loses accuracy at the tolerances in use.  The network twin of
+    ``sensitivity.analysis.local_sensitivity_batch``.  ``vary``: names (``"c_k_0"``, ``"A_i_1"``, ``"tf_scale"``, as ``compute_bounds``
+    names them) or indices into the flat parameter vector; None = every entry -- but this is a tool for a chosen handful of entries: a
+    launch costs about (1 + KC) / KC state integrations per column (KC = ``eng.sens_columns_per_launch()``), a full gradient needs an
+    adjoint.  Returns a dict with
+
+      names       the K varied entries
+      layout      the index lists (``make_index_lists``) pred's rows follow, times the union grid
+      pred        [n_obs]     fold-change observables (protein | rna | phospho), floors ``eps``
+      dpred       [n_obs, K]  their derivatives through numerator and baseline (0 through an active floor)
+      Y, dY       the scalar metric ``metric`` and d Y / d x [K]; ``metrics``: {name: (Y, dY)} for all four
+      elasticity  [K]  x_c dY_c / Y, 0 where Y == 0
+      scaled      [K]  dY_c (ub_c - lb_c) with the bounds of ``compute_bounds(params, perturbation)``
+      status      [1]  the solver's flags (OR over the column chunks); a flagged run has NaN entries
+
+    The chain from dY [T, S, K] to dpred and the metrics is host arithmetic."""
+    if metric not in _METRICS:
+        raise ValueError(f"metric must be one of {_METRICS}")
+    p = {k: (np.asarray(params[k], float) if k != "tf_scale" else float(params[k])) for k in _ORDER}
+    problem = compute_bounds(p, perturbation)
+    names = problem["names"]
+    if vary is None:
+        vidx = np.arange(len(names), dtype=np.int64)
+    else:
+        pos = {nm: i for i, nm in enumerate(names)}
+        vidx = np.array([pos[v] if isinstance(v, str) else int(v) for v in vary], dtype=np.int64)
+        if vidx.size == 0 or np.unique(vidx).size != vidx.size or vidx.min() < 0 or vidx.max() >= len(names):
+            raise ValueError("vary must hold distinct indices (or names) of the flat parameter vector")
+    x = eng.pack_params(*(p[k] for k in _ORDER))
+    times = np.unique(np.concatenate([t_prot, t_rna, t_pho]).astype(np.float64))
+    lists, ld = eng.make_index_lists(times, t_prot, t_rna, t_pho)
+    eng.free_loss(lists)
+    out = eng.simulate_sens_batch(x, times, vidx.astype(np.int32), y0=y0, rtol=rtol, atol=atol, max_steps=max_steps)
+    if out is None:
+        from .. import _capi
+        raise _capi.PhoskinError("local_sensitivity_batch: the sensitivity launch was refused: "
+                                 + (eng.ctx.lib.pk_last_error(eng.ctx.handle) or b"").decode())
+    dYt, Yt, status, _ = out
+    Yh, dYh = Yt[0].cpu().numpy(), dYt[0].cpu().numpy()
+    pred, dpred = fold_change_derivatives(observable_weights(eng, ld), ld, Yh, dYh, eps)
+    mets = metric_derivatives(pred, dpred)
+    val, grad = mets[metric]
+    xv = x[vidx]
+    width = np.array([problem["bounds"][i][1] - problem["bounds"][i][0] for i in vidx])
+    elasticity = np.zeros_like(grad) if val == 0.0 else xv * grad / val
+    return {"names": [names[i] for i in vidx], "layout": ld, "times": times, "pred": pred, "dpred": dpred, "Y": val, "dY": grad,
+            "metrics": mets, "elasticity": elasticity, "scaled": grad * width, "status": status.cpu().numpy()}
+
+
 def _worker_simulation(task_args):
     """``(idx, param_vector, names_map, original_shapes, sys, idx_sys, times_p, times_r, times_ph, metric) -> (idx, y, dfp, dfr, dfph)``:
     the reference's pool worker (sensitivity.py:143-168), one simulation.  ``run_sensitivity_analysis`` does not use it: all samples are

@@ -1,0 +1,27 @@
+"""CPU: the network-sensitivity entry points are declared in include/phoskin.h, listed in ``_capi.SYMBOLS``, exported by the library, and
+answer a null context / handle with an error code (no kernel is launched here)."""
+import re
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+NEW = ("pk_network_simulate_sens_batch", "pk_network_sens_columns_per_launch")
+
+
+def test_declared_listed_and_exported(built_lib):
+    from phoskintime_amd import _capi
+    txt = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "phoskin.h").read_text(), flags=re.S)
+    for name in NEW:
+        assert re.search(r"\b" + name + r"\s*\(", txt), name
+        assert name in _capi.SYMBOLS and hasattr(built_lib, name), name
+
+
+def test_null_handles_are_errors(built_lib):
+    from phoskintime_amd import _capi
+    assert built_lib.pk_network_sens_columns_per_launch(None) == _capi.PK_ERR_ARG
+    assert built_lib.pk_network_simulate_sens_batch(None, None, 1, None, 0, None, 0, None, 2, None, None, 0, None, None, None, None) == _capi.PK_ERR_ARG
+
+
+def test_python_layers_exist():
+    from phoskintime_amd.global_model import NetworkEngine, sensitivity
+    assert callable(NetworkEngine.simulate_sens_batch) and callable(NetworkEngine.sens_columns_per_launch)
+    assert callable(sensitivity.local_sensitivity_batch)
