@@ -489,6 +489,36 @@ int pk_network_simulate_sens_batch(pk_ctx*, pk_net*, int64_t B, const double* x,
  * 0 = not one column fits.  Pure host arithmetic. */
 int pk_network_sens_columns_per_launch(pk_net*);
 
+/* The three objectives of pk_network_simulate_objective_batch AND their exact discrete derivative with respect to K chosen entries
+ * cols[k] of the candidate vector, from ONE launch: the sensitivity integrator above differentiates the loss where the state and the
+ * chunk's tangents land on an output row (csrc/pk_network_sens.hpp, scoring flavour; csrc/pk_network_loss_grad.hpp for the point-loss
+ * and fold-change derivatives).  Neither the trajectory nor the tangent trajectory is written unless Y / dY are asked for.
+ *   Outputs, all DEVICE pointers, each optional (NULL): Y [B,T,S], dY [B,T,S,K] (as pk_network_simulate_sens_batch), pred [B,n_obs] and
+ *   dpred [B,n_obs,K] (fold changes with LOSS_FN's floor 1e-9 and their derivative -- 0 through an active floor --, in the caller's
+ *   (protein | rna | phospho) list order), loss_sums [B,3] and dsums [B,3,K] (the weighted sums and their derivative),
+ *   F [B,3] and dF [B,3,K] = dsums norm_m lambda_m + d prior / d x_c; the prior term lambda_prior 2 (p - d) / (d + 1e-6)^2 / (5 N) is non-zero
+ *   for columns in A, B, C, D, E and enters all three objectives.  With x_is_raw every derivative is with respect to the raw entry.
+ * Rules of pk_network_simulate_sens_batch: always PK_METHOD_ROS34PW2 on the general LDS kernel; an explicit PK_METHOD_ARK436,
+ * PK_METHOD_DP5 or PK_KERNEL_WORKSPACE is PK_ERR_UNSUPPORTED; cols (HOST) is checked on the host; column chunks of
+ * KC = pk_network_objective_grad_columns_per_launch, each integrating the state itself; chunk 0 writes Y, pred, loss_sums, F and n_steps;
+ * status is the OR over the chunks.  Rules of the order-3 fused objective: protein / phospho baselines are time index 0 and no rna
+ * observation lies before the rna baseline (else PK_ERR_UNSUPPORTED); a (state, time) may be observed twice; loss_mode 0..7; T equals the
+ * handle's; lambdas is required for F / dF.  PK_ERR_ARG when every output pointer is NULL, or K > 0 and dY, dpred, dsums, dF are all NULL.
+ * Every sum is one thread's sequential sum in list order (no atomics): a candidate's numbers are bit-equal alone and in any batch, and
+ * permuting cols permutes the outputs (K <= KC, maximum norm).
+ * Failure: a flagged chunk has NaN in its own columns of dsums, dF and dpred; F = fail_value and an all-NaN pred row when chunk 0 is
+ * flagged or a state of a scored row is not finite.
+ * K = 0 is pk_network_simulate_objective_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED, bit for bit (loss_sums or F required,
+ * pred must be NULL).  pk_last_error names the remedy for every refusal. */
+int pk_network_simulate_objective_grad_batch(pk_ctx*, pk_net*, pk_loss*, int64_t B, const double* x, int x_is_raw, const double* y0,
+                                             int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts,
+                                             const int32_t* cols_host, int K, int loss_mode, const double* defaults, const double* lambdas,
+                                             double fail_value, double* Y, double* dY, double* pred, double* dpred, double* loss_sums,
+                                             double* dsums, double* F, double* dF, int32_t* status, int32_t* n_steps);
+/* KC of pk_network_simulate_objective_grad_batch: as pk_network_sens_columns_per_launch, with the rna baseline, its tangents and the
+ * accumulators on top (8 N + 32 bytes, and 8 N + 24 per column).  Pure host arithmetic. */
+int pk_network_objective_grad_columns_per_launch(pk_net*);
+
 /* Timing hook for bench.py: runs `iters` back-to-back launches of pk_solve_protein_batch on the context's
  * stream between two hipEvents and returns the mean kernel time per launch in milliseconds (< 0 on error). */
 double pk_time_solve_protein_batch(pk_ctx*, int iters, int model, int n_sites, int64_t B,

@@ -27,6 +27,9 @@ hipError_t launch_net_ws_measure(const NetDev& n, const NetSolveArgs& a, long lo
 hipError_t launch_net_lds_measure(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st);
 // ... and carrying forward parameter sensitivities, one workgroup per (candidate, column chunk) (pk_inst_net_rosw_sens.hip)
 hipError_t launch_net_lds_sens(const NetDev& n, const NetSolveArgs& a, const NetSensArgs& s, long long B, int threads, size_t lds, hipStream_t st);
+// ... and scoring the loss and its gradient from those tangents as they land (pk_inst_net_rosw_sens_score.hip)
+hipError_t launch_net_lds_sens_score(const NetDev& n, const NetSolveArgs& a, const NetSensArgs& s, const NetSensScoreArgs& sc, long long B, int threads,
+                                     size_t lds, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
@@ -366,8 +369,9 @@ int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { ret
 // fused->loss_ptr set (the time-bucketed lists: the caller asked for the order-3 method or the workspace kernel) the launch runs where the
 // plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel.  fused->meas: the same lists measured
 // instead of scored (pk_network_simulate_measure_batch), on the same two kernels.  `sens`: null, or the columns of
-// pk_network_simulate_sens_batch (cols: HOST pointer; Y may then be null): the plan must be the general LDS kernel
-struct NetSensReq { const int32_t* cols_host; int K, KC; double* dY; };
+// pk_network_simulate_sens_batch (cols: HOST pointer; Y may then be null): the plan must be the general LDS kernel.  sens->score: the
+// scoring flavour (pk_network_simulate_objective_grad_batch); `fused` then carries the loss lists, the permutation and the loss outputs
+struct NetSensReq { const int32_t* cols_host; int K, KC; double* dY; const pk::NetSensScoreArgs* score = nullptr; };
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                              const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps,
                              const pk::NetSolveArgs* fused, const NetSensReq* sens = nullptr) {
@@ -383,7 +387,7 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   if (sens && plan.kernel != NetKernel::Lds)
     return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: the general LDS kernel only (S <= 1024, N <= 512, 160 KiB of LDS); the "
                                               "HBM-workspace kernel carries no tangents: difference pk_network_simulate_batch there");
-  const bool rosw_fused = fused && fused->loss_ptr;
+  const bool rosw_fused = fused && fused->loss_ptr && !sens;
   const bool measure = rosw_fused && fused->meas;
   if (measure) {
     if (plan.kernel == NetKernel::Reg || plan.kernel == NetKernel::CombReg)
@@ -439,7 +443,7 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
     a.loss_ptr = fused->loss_ptr; a.loss_prot = fused->loss_prot; a.loss_site = fused->loss_site; a.loss_lobs = fused->loss_lobs; a.loss_lw = fused->loss_lw;
     a.meas = fused->meas; a.meas_id = fused->meas_id; a.meas_n = fused->meas_n; a.meas_eps = fused->meas_eps;
     a.meas_perm = fused->meas_perm; a.meas_pred = fused->meas_pred; a.meas_metric = fused->meas_metric;
-    if (!rosw_fused && !(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
+    if (!rosw_fused && !sens && !(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
       return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: topologies 0 / 1 / 4 on the default additive integrator only; "
                                                 "use pk_network_simulate_batch + pk_network_objective_batch");
   }
@@ -545,13 +549,15 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
         const int kcl = std::min(sens->K, sens->KC);
         if ((size_t)kcl * n->d.S > 512) threads = 256;
         struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; const NetSensReq* s; long long B; int threads; size_t lds; int32_t* status; }
-            q{&n->d, &a, sens, (long long)B, threads, pk::net_sens_lds_bytes(n->d, n->nnzT, kcl), status};
+            q{&n->d, &a, sens, (long long)B, threads,
+              sens->score ? pk::net_sens_score_lds_bytes(n->d, n->nnzT, kcl) : pk::net_sens_lds_bytes(n->d, n->nnzT, kcl), status};
         auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
           const Q& r = *(const Q*)user;
           hipError_t e = hipMemcpyAsync(scratch, r.s->cols_host, (size_t)r.s->K * sizeof(int32_t), hipMemcpyHostToDevice, s);
           if (e == hipSuccess && r.status) e = hipMemsetAsync(r.status, 0, (size_t)r.B * sizeof(int32_t), s);
           if (e != hipSuccess) return e;
           const pk::NetSensArgs sa{(const int32_t*)scratch, r.s->K, r.s->KC, r.s->dY};
+          if (r.s->score) return pk::launch_net_lds_sens_score(*r.d, *r.a, sa, *r.s->score, r.B, r.threads, r.lds, s);
           return pk::launch_net_lds_sens(*r.d, *r.a, sa, r.B, r.threads, r.lds, s);
         };
         return pk_ctx_scratch_launch(c, (size_t)sens->K * sizeof(int32_t), launch, &q);
@@ -693,6 +699,84 @@ int pk_network_simulate_sens_batch(pk_ctx* c, pk_net* n, int64_t B, const double
                                               "network, or it is beyond the LDS kernel (S <= 1024, N <= 512); difference pk_network_simulate_batch");
   const NetSensReq req{cols_host, K, KC, dY};
   return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr, &req);
+}
+
+// Columns one workgroup of the scoring flavour carries: as pk_network_sens_columns_per_launch with net_sens_score_lds_bytes (the rna
+// baseline, its tangents and the accumulators come on top): same 160 KiB, same n_var cap, same dev knob
+int pk_network_objective_grad_columns_per_launch(pk_net* n) {
+  if (!n) return PK_ERR_ARG;
+  if (n->d.S > 1024 || n->d.N > 512) return 0;
+  int kc = std::min(pk::net_sens_score_max_columns(n->d, n->nnzT, 160 * 1024), n->d.n_var);
+  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < kc) kc = v; }
+  return kc;
+}
+
+// The three objectives AND their derivative with respect to x[cols] from one integration of the augmented system: the scoring flavour of
+// the sensitivity kernel differentiates the loss where state and tangents land on an output row (pk_network_sens.hpp); neither the
+// trajectory nor the tangent trajectory reaches HBM unless Y / dY are asked for.  Rules of pk_network_simulate_sens_batch (order-3 method,
+// general LDS kernel, cols checked here) and of the order-3 fused objective (the time-bucketed lists).  K = 0 is
+// pk_network_simulate_objective_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED
+int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_t B, const double* x, int x_is_raw, const double* y0,
+                                             int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host,
+                                             int K, int loss_mode, const double* defaults, const double* lambdas, double fail_value, double* Y,
+                                             double* dY, double* pred, double* dpred, double* loss_sums, double* dsums, double* F, double* dF,
+                                             int32_t* status, int32_t* n_steps) {
+  if (!c || !n || !l) return PK_ERR_ARG;
+  if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
+  if (K < 0) return pk_ctx_fail(c, PK_ERR_ARG, "K must be >= 0");
+  if (opts && (opts->method == PK_METHOD_ARK436 || opts->method == PK_METHOD_DP5))
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients integrate with PK_METHOD_ROS34PW2 only: leave opts->method at its default or ask for "
+                                              "PK_METHOD_ROS34PW2");
+  if (opts && opts->kernel == PK_KERNEL_WORKSPACE)
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients run on the general LDS kernel only (the workspace kernel carries no tangents): leave "
+                                              "opts->kernel at PK_KERNEL_AUTO");
+  if (loss_mode < 0 || loss_mode > 7) return pk_ctx_fail(c, PK_ERR_ARG, "loss_mode must be 0..7");
+  if (!Y && !dY && !pred && !dpred && !loss_sums && !dsums && !F && !dF)
+    return pk_ctx_fail(c, PK_ERR_ARG, "every output pointer is NULL: pass at least one of Y, dY, pred, dpred, loss_sums, dsums, F, dF");
+  if (K > 0 && !dY && !dpred && !dsums && !dF)
+    return pk_ctx_fail(c, PK_ERR_ARG, "K > 0 but dY, dpred, dsums and dF are all NULL: pass one of them, or K = 0 for the objectives alone");
+  if ((F || dF) && !lambdas) return pk_ctx_fail(c, PK_ERR_ARG, "lambdas (protein, rna, phospho, prior) are required for F and dF");
+  if (K > 0) {
+    if (!cols_host) return pk_ctx_fail(c, PK_ERR_ARG, "cols is NULL with K > 0");
+    std::vector<char> seen((size_t)n->d.n_var, 0);
+    for (int k = 0; k < K; ++k) {
+      const int col = cols_host[k];
+      if (col < 0 || col >= n->d.n_var) return pk_ctx_fail(c, PK_ERR_ARG, "cols: index outside [0, n_var)");
+      if (seen[col]) return pk_ctx_fail(c, PK_ERR_ARG, "cols: an index is repeated");
+      seen[col] = 1;
+    }
+  }
+  pk_solver_opts o;
+  if (opts) o = *opts; else pk_default_opts(&o);
+  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = PK_KERNEL_AUTO;
+  if (K == 0) {
+    if (pred || (!loss_sums && !F))
+      return pk_ctx_fail(c, PK_ERR_ARG, "K = 0 computes loss_sums / F (and Y) as pk_network_simulate_objective_batch does: pass one of them, and ask "
+                                        "pk_network_simulate_measure_batch for pred");
+    return pk_network_simulate_objective_batch(c, n, l, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, loss_mode, defaults, lambdas, fail_value, Y,
+                                               status, n_steps, loss_sums, F);
+  }
+  pk::NetSolveArgs f;
+  std::memset(&f, 0, sizeof(f));
+  int Tl = 0, Tm = 0, rb = 0;
+  const int32_t *p2 = nullptr, *pr2 = nullptr, *si2 = nullptr;
+  if (!pk_loss_fused_lists(l, &f.loss_ptr, &f.loss_prot, &f.loss_site, &f.loss_lobs, &f.loss_lw, f.loss_norm, &Tl, &f.loss_rna_base) ||
+      !pk_loss_measure_lists(l, &p2, &pr2, &si2, &f.meas_perm, &f.meas_n, &Tm, &rb))
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients: protein / phospho baselines must be time index 0 and rna observations not earlier "
+                                              "than the rna baseline; difference pk_network_simulate_batch + pk_network_objective_batch");
+  if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the loss data were created for");
+  if (B == 0) return PK_OK;
+  const int KC = pk_network_objective_grad_columns_per_launch(n);
+  if (KC < 1)
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients: not one tangent column fits beside the state in one workgroup's LDS (160 KiB) on this "
+                                              "network, or it is beyond the LDS kernel (S <= 1024, N <= 512); difference pk_network_simulate_objective_batch");
+  f.loss_defaults = defaults; f.loss_mode = loss_mode; f.loss_fail = fail_value; f.loss_sums = loss_sums; f.loss_F = F;
+  f.loss_lam[0] = lambdas ? lambdas[0] : 1.0; f.loss_lam[1] = lambdas ? lambdas[1] : 1.0; f.loss_lam[2] = lambdas ? lambdas[2] : 1.0;
+  f.loss_lam[3] = lambdas ? lambdas[3] : 0.0;
+  f.meas_pred = pred;
+  const pk::NetSensScoreArgs sc{dpred, dsums, dF};
+  const NetSensReq req{cols_host, K, KC, dY, &sc};
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, &f, &req);
 }
 
 int pk_network_unpack_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x_raw, double* x_phys) {

@@ -22,8 +22,23 @@
 //
 // With x_is_raw the derivative is with respect to the raw entry: the physical tangent is integrated (so the steps do not depend on the
 // parametrisation) and every stored value is multiplied by softplus'(raw) -- exactly 1 where softplus returns its argument.
+//
+// Output policy (NetSensOut).  SENS_STORE writes dY and nothing else.  SENS_SCORE differentiates the three-objective loss where the state
+// and the chunk's tangents land on an output row (pk_network_simulate_objective_grad_batch): the step loop is the same statement for
+// statement; only row 0 and a landing with row >= 0 differ.  The loss handle's time-bucketed lists are walked as net_rosw_solve<..,
+// SCORE_LOSS>'s score_row walks them.  A row's entries (protein | rna | phospho) are taken in tiles of S through the stage vectors Ys, U1,
+// U2, U3, which are dead between an accepted step and the next factorisation: a first pass, one thread per entry, leaves numerator a,
+// baseline c, w rho'(pred) and w rho(pred) there (and stores pred); then ONE thread per (modality, column) walks the tile's entries of its
+// modality in list order, forms da, dc from the column's tangent, and adds w rho' dpred_c to its accumulator dacc[m][c] (LDS, 3 kc doubles;
+// the thread of column 0 also adds w rho to lacc[m]).  No reduction and no atomic: every sum is one thread's sequential sum in list order,
+// so a candidate's numbers do not depend on the batch, on B or on the position of its column inside the chunk.  dpred is written by
+// threads over (entry, column) pairs.  Baselines: y0 for protein / phospho (data: dc = 0); the rna baseline row and its kc tangent rows are
+// kept from the landing that produces them (N (1 + kc) doubles of LDS).  Chunk 0 writes pred, loss_sums and F (fail_value under the rule
+// of net_rosw_solve); every chunk writes its own columns of dpred, dsums and dF = dsums norm_m lambda_m + d prior / d x_c, NaN if the chunk
+// is flagged.  With x_is_raw every derivative is multiplied by softplus'(raw), as dY is.
 #pragma once
 #include "pk_network_solve.hpp"
+#include "pk_network_loss_grad.hpp"
 
 namespace pk {
 
@@ -31,6 +46,15 @@ struct NetSensArgs {
   const int32_t* cols;     // [K] (device): indices into the candidate vector, NetSlices order; distinct, in range (the host checks)
   int K, KC;               // columns asked for; columns per workgroup
   double* dY;              // [B, T, S, K], K contiguous
+};
+
+// what a sensitivity workgroup does with an output row: store the tangents, or score the loss and its gradient (and store on request)
+enum NetSensOut : int { SENS_STORE = 0, SENS_SCORE = 1 };
+// outputs of the scoring flavour beyond NetSolveArgs' (loss_sums, loss_F, meas_pred with meas_perm / meas_n); each optional
+struct NetSensScoreArgs {
+  double* dpred;           // [B, n_obs, K], caller's list order
+  double* dsums;           // [B, 3, K]
+  double* dF;              // [B, 3, K]
 };
 
 constexpr double SENS_DIVERGED = 1e100;
@@ -46,6 +70,17 @@ __host__ inline int net_sens_max_columns(const NetDev& n, int nnzT, size_t budge
   const size_t fixed = net_sens_lds_bytes(n, nnzT, 0);
   if (fixed >= budget) return 0;
   return (int)((budget - fixed) / (net_sens_col_doubles(n) * 8));
+}
+
+// The scoring flavour adds, behind the store flavour's request: the rna baseline (N) and per column its tangent (N), the accumulators
+// dacc [3, kc] and lacc [3] (+ 1 of padding)
+__host__ __device__ inline size_t net_sens_score_lds_bytes(const NetDev& n, int nnzT, int kc) {
+  return net_sens_lds_bytes(n, nnzT, kc) + ((size_t)n.N + 4 + (size_t)kc * ((size_t)n.N + 3)) * 8;
+}
+__host__ inline int net_sens_score_max_columns(const NetDev& n, int nnzT, size_t budget) {
+  const size_t fixed = net_sens_score_lds_bytes(n, nnzT, 0);
+  if (fixed >= budget) return 0;
+  return (int)((budget - fixed) / ((net_sens_col_doubles(n) + n.N + 3) * 8));
 }
 
 // d/d eps of net_state_rhs_ctx at (p + eps e_col, y + eps s), Sall + eps dSr, synth + eps dsynth: the tangent of state (i, loc)
@@ -121,12 +156,15 @@ __device__ __forceinline__ double net_state_rhs_tan(const NetDev& n, const NetLd
 }
 
 // ROS34PW2-W of candidate b with the columns [c0, c0 + kc) of S.cols.  L, base, red, lay: as net_rosw_solve; ext: the extra LDS
-// (net_sens_lds_bytes - net_solve_lds_bytes of it).  The state part is net_rosw_solve<MODEL, SCORE_NONE>'s, statement for statement
-template <int MODEL, class Layout>
-__device__ __forceinline__ void net_rosw_sens_solve(const NetDev& n, const NetSolveArgs& A, const NetSensArgs& SA, const Layout& lay, const long long b,
-                                                    const int c0, const int kc, NetLds L, double* const base, double* const red, double* const ext) {
+// (net_sens_lds_bytes - net_solve_lds_bytes of it; SENS_SCORE: net_sens_score_lds_bytes - ...).  The state part is
+// net_rosw_solve<MODEL, SCORE_NONE>'s, statement for statement.  SC: the scoring flavour's outputs (SENS_STORE: unused, null)
+template <int MODEL, NetSensOut OUT, class Layout>
+__device__ __forceinline__ void net_rosw_sens_solve(const NetDev& n, const NetSolveArgs& A, const NetSensArgs& SA, const NetSensScoreArgs* const SC,
+                                                    const Layout& lay, const long long b, const int c0, const int kc, NetLds L, double* const base,
+                                                    double* const red, double* const ext) {
   using namespace rosw;
   constexpr int model = MODEL;
+  constexpr bool SCORE = OUT == SENS_SCORE;
   const int S = n.S, N = n.N, K = SA.K;
   double* y = L.y;
   double* Ys = base;
@@ -165,14 +203,116 @@ __device__ __forceinline__ void net_rosw_sens_solve(const NetDev& n, const NetSo
   const double* y0 = A.y0 + (A.y0_batched ? b * S : 0);
   const bool wY = chunk0 && A.Y != nullptr;
   double* Yout = wY ? A.Y + b * (size_t)A.T * S : nullptr;
-  double* dYout = SA.dY + b * (size_t)A.T * S * K + c0;       // entry (row, k, c): dYout[((size_t)row * S + k) * K + c]
+  const bool wdY = !SCORE || SA.dY != nullptr;                // the store flavour always has dY
+  double* dYout = wdY ? SA.dY + b * (size_t)A.T * S * K + c0 : nullptr;       // entry (row, k, c): dYout[((size_t)row * S + k) * K + c]
   for (int k = tid; k < S; k += nt) { const double v = y0[k]; y[k] = v; if (wY) Yout[k] = v; }
   for (int q = tid; q < kc * S; q += nt) {
     const int c = q / S, k = q - c * S;
     col_s(c)[k] = 0.0;
-    dYout[(size_t)k * K + c] = 0.0;
+    if (wdY) dYout[(size_t)k * K + c] = 0.0;
   }
+  // ---- scoring flavour: its LDS behind the columns' vectors, and what it does with output row `row`, which y and col_s(c) hold
+  double* const rbase = tan0 + (size_t)kc * cst;              // rna baseline row
+  double* const drb = rbase + N;                              // its tangent, per column
+  double* const dacc = drb + (size_t)kc * N;                  // [3, kc]: sum of w rho' dpred_c per modality and column
+  double* const lacc = dacc + 3 * (size_t)kc;                 // [3]: sum of w rho per modality
+  bool ybad = false;
+  double* const predb = (SCORE && chunk0 && A.meas_pred) ? A.meas_pred + b * (size_t)A.meas_n : nullptr;
+  double* const dpredb = (SCORE && SC->dpred) ? SC->dpred + b * (size_t)A.meas_n * K + c0 : nullptr;      // entry (o, c): dpredb[(size_t)o * K + c]
+  if constexpr (SCORE) for (int q = tid; q < 3 * kc + 3; q += nt) dacc[q] = 0.0;
   __syncthreads();
+  auto score_row = [&](const int row) {
+    if constexpr (SCORE) {
+      if (chunk0) for (int k = tid; k < S; k += nt) if (nonfinite(y[k])) ybad = true;
+      if (row == A.loss_rna_base) {
+        for (int q = tid; q < (1 + kc) * N; q += nt) {
+          const int c = q / N, i = q - c * N;
+          const int st = n.offset_y[i];
+          if (c == 0) rbase[i] = y[st]; else drb[(size_t)(c - 1) * N + i] = col_s(c - 1)[st];
+        }
+        __syncthreads();
+      }
+      const int T1 = A.T + 1;
+      const int32_t* ptr = A.loss_ptr + row;
+      const int b0 = ptr[0], n0 = ptr[1] - b0, b1 = ptr[T1], n1 = ptr[T1 + 1] - b1, b2 = ptr[2 * T1], n2 = ptr[2 * T1 + 1] - b2;
+      const int ntot = n0 + n1 + n2;
+      // position v in the row's (protein | rna | phospho) entries -> modality and list entry
+      auto locate = [&](const int v, int& m, int& k) {
+        if (v < n0) { m = 0; k = b0 + v; } else if (v < n0 + n1) { m = 1; k = b1 + (v - n0); } else { m = 2; k = b2 + (v - n0 - n1); }
+      };
+      // numerator and baseline of an entry, summed as net_rosw_solve's score_row sums them
+      auto entry_val = [&](const int m, const int k, double& a, double& c) {
+        const int i = A.loss_prot[k], st = n.offset_y[i];
+        if (m == 0) {
+          const int cnt = (model == 2) ? (1 << n.n_sites[i]) : 1 + n.n_sites[i];
+          a = 0.0; c = 0.0;
+          for (int m_ = 0; m_ < cnt; ++m_) { a += y[st + 1 + m_]; c += y0[st + 1 + m_]; }
+        } else if (m == 1) { a = y[st]; c = rbase[i]; }
+        else {
+          const int j = A.loss_site[k];
+          if (model == 2) {
+            a = 0.0; c = 0.0;
+            const int cnt = 1 << n.n_sites[i];
+            for (int m_ = 0; m_ < cnt; ++m_) if (m_ & (1 << j)) { a += y[st + 1 + m_]; c += y0[st + 1 + m_]; }
+          } else { a = y[st + 2 + j]; c = y0[st + 2 + j]; }
+        }
+      };
+      // the same sums over column cc's tangent; the protein / phospho baseline is data
+      auto entry_tan = [&](const int m, const int k, const int cc, double& da, double& dc) {
+        const int i = A.loss_prot[k], st = n.offset_y[i];
+        const double* sv = col_s(cc);
+        dc = 0.0;
+        if (m == 0) {
+          const int cnt = (model == 2) ? (1 << n.n_sites[i]) : 1 + n.n_sites[i];
+          da = 0.0;
+          for (int m_ = 0; m_ < cnt; ++m_) da += sv[st + 1 + m_];
+        } else if (m == 1) { da = sv[st]; dc = drb[(size_t)cc * N + i]; }
+        else {
+          const int j = A.loss_site[k];
+          if (model == 2) {
+            da = 0.0;
+            const int cnt = 1 << n.n_sites[i];
+            for (int m_ = 0; m_ < cnt; ++m_) if (m_ & (1 << j)) da += sv[st + 1 + m_];
+          } else da = sv[st + 2 + j];
+        }
+      };
+      double* const tA = Ys; double* const tC = U1; double* const tG = U2; double* const tL = U3;      // dead until the next step
+      for (int v0 = 0; v0 < ntot; v0 += S) {
+        const int nv = min(S, ntot - v0);
+        for (int e = tid; e < nv; e += nt) {
+          int m, k; locate(v0 + e, m, k);
+          double a, c; entry_val(m, k, a, c);
+          const double obs = A.loss_lobs[k], w = A.loss_lw[k], pred = fold_change(a, c);
+          tA[e] = a; tC[e] = c;
+          tG[e] = w * point_loss_dpred(A.loss_mode, obs, pred);
+          tL[e] = w * point_loss(A.loss_mode, obs - pred, obs, pred);
+          if (predb) predb[A.meas_perm[k]] = pred;
+        }
+        __syncthreads();
+        for (int q = tid; q < 3 * kc; q += nt) {
+          const int m = q / kc, cc = q - m * kc;
+          const int lo = m == 0 ? 0 : (m == 1 ? n0 : n0 + n1), cntm = m == 0 ? n0 : (m == 1 ? n1 : n2), kb = m == 0 ? b0 : (m == 1 ? b1 : b2);
+          const int e0 = max(lo - v0, 0), e1 = min(lo + cntm - v0, nv);
+          double acc = dacc[q], ls = lacc[m];
+          for (int e = e0; e < e1; ++e) {
+            double da, dc; entry_tan(m, kb + (v0 + e - lo), cc, da, dc);
+            acc += tG[e] * fold_change_tangent(tA[e], tC[e], da, dc);
+            ls += tL[e];
+          }
+          dacc[q] = acc;
+          if (cc == 0) lacc[m] = ls;
+        }
+        if (dpredb) for (int q = tid; q < nv * kc; q += nt) {
+          const int e = q / kc, cc = q - e * kc;
+          int m, k; locate(v0 + e, m, k);
+          double da, dc; entry_tan(m, k, cc, da, dc);
+          dpredb[(size_t)A.meas_perm[k] * K + cc] = fold_change_tangent(tA[e], tC[e], da, dc) * scl[cc];
+        }
+        __syncthreads();
+      }
+    }
+  };
+  score_row(0);
 
   auto factor = [&](const double g) {
     lay.prots([&](const int i, const int st, const int ss, const int ns, const int) {
@@ -434,10 +574,11 @@ __device__ __forceinline__ void net_rosw_sens_solve(const NetDev& n, const NetSo
     const int row = stop_out[si];
     if (row >= 0) {
       if (wY) for (int k = tid; k < S; k += nt) Yout[(size_t)row * S + k] = y[k];
-      for (int q = tid; q < kc * S; q += nt) {
+      if (wdY) for (int q = tid; q < kc * S; q += nt) {
         const int c = q / S, k = q - c * S;
         dYout[((size_t)row * S + k) * K + c] = col_s(c)[k] * scl[c];
       }
+      score_row(row);
     }
     const int jn = net_bucket(tc, n.kin_grid, n.n_grid);
     if (jn != jb) { jb = jn; net_prepare_bucket(n, L, jb); prepare_bucket_tan(); }
@@ -451,13 +592,58 @@ __device__ __forceinline__ void net_rosw_sens_solve(const NetDev& n, const NetSo
       if (row < 0) continue;
       const bool missed = !(stops[si] <= tc);
       if (missed && wY) for (int k = tid; k < S; k += nt) Yout[(size_t)row * S + k] = qnan;
-      if (missed || all) for (int q = tid; q < kc * S; q += nt) { const int c = q / S, k = q - c * S; dYout[((size_t)row * S + k) * K + c] = qnan; }
+      if (wdY && (missed || all)) for (int q = tid; q < kc * S; q += nt) { const int c = q / S, k = q - c * S; dYout[((size_t)row * S + k) * K + c] = qnan; }
     }
-    if (all) for (int q = tid; q < kc * S; q += nt) { const int c = q / S, k = q - c * S; dYout[(size_t)k * K + c] = qnan; }
+    if (wdY && all) for (int q = tid; q < kc * S; q += nt) { const int c = q / S, k = q - c * S; dYout[(size_t)k * K + c] = qnan; }
   }
   if (tid == 0) {
     if (A.status && status != PK_ST_OK) atomicOr(A.status + b, status);
     if (A.n_steps && chunk0) { A.n_steps[2 * b] = nacc; A.n_steps[2 * b + 1] = nrej; }
+  }
+  if constexpr (SCORE) {
+    // the chunk's columns of dsums and dF (a barrier of score_row lies behind the last accumulation); a flagged chunk has none to trust
+    const double qnan = __builtin_nan("");
+    const bool flagged = status != PK_ST_OK;
+    for (int q = tid; q < 3 * kc; q += nt) {
+      const int m = q / kc, cc = q - m * kc, col = colv[cc];
+      double dprior = 0.0;
+      if (A.loss_defaults && ((col >= sl.A && col < sl.Dp) || (col >= sl.E && col < sl.tf))) {
+        const double d = A.loss_defaults[col], den = d + 1e-6;
+        dprior = A.loss_lam[3] * ((2.0 * (L.p[col] - d)) / (den * den) / (double)(5 * N));
+      }
+      const double ds = flagged ? qnan : dacc[q] * scl[cc];
+      const double dFv = flagged ? qnan : ((dacc[q] * A.loss_norm[m]) * A.loss_lam[m] + dprior) * scl[cc];
+      const size_t at = ((size_t)b * 3 + m) * K + c0 + cc;
+      if (SC->dsums) SC->dsums[at] = ds;
+      if (SC->dF) SC->dF[at] = dFv;
+    }
+    __syncthreads();                                    // the dpred entries written at the rows lie behind this barrier
+    if (flagged && dpredb) for (int q = tid; q < A.meas_n * kc; q += nt) { const int o = q / kc, cc = q - o * kc; dpredb[(size_t)o * K + cc] = qnan; }
+    if (chunk0) {
+      // objective assembly as net_rosw_solve<.., SCORE_LOSS> does it, from the list-order sums
+      double prior = 0.0;
+      if (A.loss_defaults) {
+        double acc = 0.0;
+        for (int k = tid; k < 5 * N; k += nt) {
+          const int grp = k / N, i = k - grp * N;
+          const int off = (grp == 0 ? sl.A : grp == 1 ? sl.B : grp == 2 ? sl.C : grp == 3 ? sl.D : sl.E) + i;
+          const double d = (L.p[off] - A.loss_defaults[off]) / (A.loss_defaults[off] + 1e-6);
+          acc = __builtin_fma(d, d, acc);
+        }
+        prior = A.loss_lam[3] * (block_sum(acc, red) / (double)(5 * N));
+      }
+      const bool bad = block_max(ybad ? 1.0 : 0.0, red) != 0.0 || flagged;
+      if (bad && predb) for (int k = tid; k < A.meas_n; k += nt) predb[k] = qnan;
+      if (tid == 0) {
+        const double lp = lacc[0], lr = lacc[1], lph = lacc[2];
+        if (A.loss_sums) { A.loss_sums[3 * b] = lp; A.loss_sums[3 * b + 1] = lr; A.loss_sums[3 * b + 2] = lph; }
+        if (A.loss_F) {
+          A.loss_F[3 * b] = bad ? A.loss_fail : (lp * A.loss_norm[0]) * A.loss_lam[0] + prior;
+          A.loss_F[3 * b + 1] = bad ? A.loss_fail : (lr * A.loss_norm[1]) * A.loss_lam[1] + prior;
+          A.loss_F[3 * b + 2] = bad ? A.loss_fail : (lph * A.loss_norm[2]) * A.loss_lam[2] + prior;
+        }
+      }
+    }
   }
 }
 
@@ -479,7 +665,29 @@ __global__ __launch_bounds__(256) void net_solve_sens_kernel(const NetDev n, con
   const NetRegLayout lay(n, tf_dat, tf_deg, tf_ptr, tf_idx);
   const int c0 = blockIdx.y * SA.KC;
   const int kc = min(SA.KC, SA.K - c0);
-  net_rosw_sens_solve<MODEL>(n, A, SA, lay, blockIdx.x, c0, kc, NetLds(lds, n), lds + NetLds::doubles(n), red, lds + net_solve_lds_bytes(n, nnzT) / 8);
+  net_rosw_sens_solve<MODEL, SENS_STORE>(n, A, SA, nullptr, lay, blockIdx.x, c0, kc, NetLds(lds, n), lds + NetLds::doubles(n), red,
+                                         lds + net_solve_lds_bytes(n, nnzT) / 8);
+}
+
+// The scoring flavour (NetSensOut above): the same grid and the same LDS layout, net_sens_score_lds_bytes of it; SA.dY may be null
+template <int MODEL>
+__global__ __launch_bounds__(256) void net_solve_sens_score_kernel(const NetDev n, const NetSolveArgs A, const NetSensArgs SA, const NetSensScoreArgs SC) {
+  extern __shared__ __align__(16) double lds[];
+  const int N = n.N, nnzT = n.TF_indptr[N];
+  double* red = lds + net_rosw_doubles(n);
+  double* tf_dat = red + 24;
+  double* tf_deg = tf_dat + nnzT;
+  int32_t* tf_ptr = reinterpret_cast<int32_t*>(tf_deg + N);
+  int32_t* tf_idx = tf_ptr + (N + 1);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int k = tid; k < nnzT; k += nt) { tf_dat[k] = n.TF_data[k]; tf_idx[k] = n.TF_indices[k]; }
+  for (int k = tid; k <= N; k += nt) tf_ptr[k] = n.TF_indptr[k];
+  for (int k = tid; k < N; k += nt) tf_deg[k] = n.tf_deg[k];
+  const NetRegLayout lay(n, tf_dat, tf_deg, tf_ptr, tf_idx);
+  const int c0 = blockIdx.y * SA.KC;
+  const int kc = min(SA.KC, SA.K - c0);
+  net_rosw_sens_solve<MODEL, SENS_SCORE>(n, A, SA, &SC, lay, blockIdx.x, c0, kc, NetLds(lds, n), lds + NetLds::doubles(n), red,
+                                         lds + net_solve_lds_bytes(n, nnzT) / 8);
 }
 
 }  // namespace pk

@@ -362,6 +362,82 @@ class NetworkEngine:
         dY._keepalive = (xd, yd, ch)  # type: ignore[attr-defined]
         return dY, Y, status, nsteps
 
+    def objective_grad_columns_per_launch(self) -> int:
+        """Tangent columns one workgroup of ``simulate_objective_grad_batch`` carries on this network
+        (``pk_network_objective_grad_columns_per_launch``: host arithmetic on the LDS budget); 0 when not even one fits."""
+        return int(_capi.load().pk_network_objective_grad_columns_per_launch(self._h))
+
+    def simulate_objective_grad_batch(self, loss, x, t_eval, cols, y0=None, raw: bool = False, rtol: Optional[float] = None,
+                                      atol: Optional[float] = None, max_steps: int = 1000000, err_norm: str = "max", loss_mode: int = 0,
+                                      defaults=None, lambdas=(1.0, 1.0, 1.0, 0.0), fail_value: float = 1e12, want_F: bool = True,
+                                      want_sums: bool = True, want_pred: bool = False, want_Y: bool = False, want_dY: bool = False,
+                                      method: str = "auto", kernel: str = "auto"):
+        """The three objectives AND their exact discrete derivative with respect to the entries ``cols`` of the candidate vector from ONE
+        launch (``pk_network_simulate_objective_grad_batch``): the sensitivity integrator of ``simulate_sens_batch`` differentiates the loss
+        of the handle ``loss`` where state and tangents land on an output row; neither the trajectory nor the tangent trajectory reaches
+        HBM unless asked for.  Returns a dict of GPU tensors -- ``status`` [B], ``n_steps`` [B, 2], and as asked: ``F`` [B, 3] and ``dF``
+        [B, 3, K] (``want_F``), ``loss_sums`` [B, 3] and ``dsums`` [B, 3, K] (``want_sums``), ``pred`` [B, n_obs] and ``dpred``
+        [B, n_obs, K] in the order of the lists as given (``want_pred``), ``Y`` (``want_Y``), ``dY`` (``want_dY``) -- or ``None`` when the
+        launch is refused (PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy): ``method`` "ark" / "dp5", ``kernel="workspace"``, an
+        rna observation before the rna baseline, or a network on which no column fits.  ``raw=True``: derivatives with respect to the raw
+        entries.  Tolerances default to the order-3 kernel's 1e-7 / 1e-9.  ``objective_grad_columns_per_launch()`` columns share one
+        workgroup; every chunk of columns integrates the state itself.  A candidate's numbers are bit-equal alone and in any batch.  With
+        no columns the call is ``simulate_objective_batch(method="rosw", kernel="lds")``.  A full gradient over all ``n_var`` columns
+        costs n_var / KC state integrations: this is a tool for a gradient polish or a Gauss-Newton step on chosen parameters."""
+        if method not in ("auto", "ark", "rosw", "dp5"):
+            raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
+        if kernel not in ("auto", "lds", "workspace"):
+            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
+        if loss not in self._n_obs:
+            raise ValueError("loss must be a handle made by this engine's make_loss / make_index_lists (and not freed)")
+        rtol = 1e-7 if rtol is None else rtol
+        atol = 1e-9 if atol is None else atol
+        dev = torch.device("cuda", self.ctx.device)
+        xd = _dev_f64(x, dev)
+        if xd.dim() == 1:
+            xd = xd.unsqueeze(0)
+        if xd.shape[1] != self.n_var:
+            raise ValueError(f"x must be [B, {self.n_var}]")
+        B = xd.shape[0]
+        yd = _dev_f64(self.default_y0() if y0 is None else y0, dev)
+        if yd.shape == (self.S,):
+            yb = 0
+        elif yd.shape == (B, self.S):
+            yb = 1
+        else:
+            raise ValueError(f"y0 must be [{self.S}] or [{B}, {self.S}]")
+        th = np.ascontiguousarray(np.atleast_1d(np.asarray(t_eval, dtype=np.float64)))
+        T = th.size
+        ch = _i32(np.atleast_1d(cols)).reshape(-1)
+        K = int(ch.size)
+        n_obs = self._n_obs[loss]
+        dd = _dev_f64(defaults, dev) if defaults is not None else None
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        out = {"status": torch.zeros((B,), dtype=torch.int32, device=dev), "n_steps": torch.zeros((B, 2), dtype=torch.int32, device=dev)}
+        if want_F:
+            out["F"] = new(B, 3); out["dF"] = new(B, 3, K)
+        if want_sums:
+            out["loss_sums"] = new(B, 3); out["dsums"] = new(B, 3, K)
+        if want_pred and K:
+            out["pred"] = new(B, n_obs); out["dpred"] = new(B, n_obs, K)
+        if want_Y:
+            out["Y"] = new(B, T, self.S)
+        if want_dY:
+            out["dY"] = new(B, T, self.S, K)
+        lam = (C.c_double * 4)(*[float(v) for v in lambdas])
+        opts = self._opts(method, kernel, rtol=rtol, atol=atol, max_steps=max_steps, err_norm=err_norm)
+        g = lambda k: _ptr(out.get(k)) if (K or k in ("Y", "loss_sums", "F")) else None
+        self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self.ctx.lib.pk_network_simulate_objective_grad_batch(
+            self.ctx.handle, self._h, loss, B, _ptr(xd), int(raw), _ptr(yd), yb, th.ctypes.data, T, C.byref(opts), ch.ctypes.data if K else None, K,
+            int(loss_mode), _ptr(dd), C.cast(lam, C.c_void_p), float(fail_value), g("Y"), g("dY"), g("pred"), g("dpred"), g("loss_sums"),
+            g("dsums"), g("F"), g("dF"), _ptr(out["status"]), _ptr(out["n_steps"]))
+        if rc == _capi.PK_ERR_UNSUPPORTED:
+            return None
+        self.ctx.check(rc)
+        out["status"]._keepalive = (xd, yd, dd, ch)  # type: ignore[attr-defined]
+        return out
+
     def resolved_method(self, method: str = "auto", kernel: str = "auto") -> str:
         """The integrator ``simulate_batch(method=, kernel=)`` will run on this network -- "ark", "rosw" or "dp5" -- as decided by the
         library itself (``pk_network_resolve_method``: network size, sites per protein AND the LDS footprint of the order-4 kernel).

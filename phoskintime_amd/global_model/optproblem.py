@@ -67,6 +67,21 @@ class GlobalODEBatch:
                                         fail_value=self.fail_value, status=status)
         return F
 
+    def evaluate_with_grad(self, X, cols):
+        """X [b, n_var] raw, ``cols`` [K] indices into the candidate vector -> (F [b, 3], dF [b, 3, K]) on the device: the objectives
+        and their exact discrete derivative with respect to the RAW entries ``cols`` from one launch
+        (``NetworkEngine.simulate_objective_grad_batch`` with the problem's tolerances, loss mode, defaults and lambdas).  F comes from
+        the order-3 integrator with the tangents in its error norm, so it is within the tolerances of ``evaluate_device``'s, not
+        bit-equal to it.  Raises PhoskinError where the launch is refused (``pk_last_error`` names the remedy)."""
+        out = self.eng.simulate_objective_grad_batch(
+            self.loss, X, self.time_grid, cols, y0=self.y0, raw=True, rtol=self.rtol, atol=self.atol, max_steps=self.max_steps * self.time_grid.size,
+            err_norm=self.err_norm, loss_mode=self.loss_mode, defaults=self.defaults, lambdas=self.lam, fail_value=self.fail_value,
+            want_sums=False)
+        if out is None:
+            from .. import _capi
+            raise _capi.PhoskinError("evaluate_with_grad: " + (self.eng.ctx.lib.pk_last_error(self.eng.ctx.handle) or b"").decode())
+        return out["F"], out["dF"]
+
     def evaluate(self, X) -> np.ndarray:
         """X [B, n_var] raw -> F [B, 3] (host).  Under an initialised ``torch.distributed`` group the candidates are dealt round-robin over
         the ranks (one process per GPU) in decreasing order of a stiffness proxy -- the largest physical rate of the candidate, which is what
