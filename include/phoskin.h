@@ -105,8 +105,12 @@ enum {
   PK_KERNEL_AUTO  = 0,  /* by batch size (default)                                                             */
   PK_KERNEL_GROUP = 1,  /* lane-group kernels (several lanes per replica) at every batch size                  */
   PK_KERNEL_TPR   = 2,  /* thread-per-replica kernels wherever one exists for (model, n_sites), else lane-group */
-  PK_KERNEL_WORKSPACE = 3  /* pk_network_simulate_batch only: ROS34PW2 on the HBM-workspace kernel at any network size (the kernel
+  PK_KERNEL_WORKSPACE = 3, /* pk_network_simulate_batch only: ROS34PW2 on the HBM-workspace kernel at any network size (the kernel
                               networks beyond one workgroup's LDS take by themselves)                                           */
+  PK_KERNEL_HBM = 4        /* pk_network_simulate_sens_batch and pk_network_simulate_objective_grad_batch only: state AND tangents on
+                              HBM slabs at any network size (the route networks beyond one workgroup's LDS take by themselves).
+                              Every other network entry point answers PK_ERR_UNSUPPORTED for it (pk_network_resolve_method too) and the
+                              per-protein entry points PK_ERR_ARG ("unknown opts->kernel"), as they do for PK_KERNEL_WORKSPACE     */
 };
 
 typedef struct pk_ctx pk_ctx;
@@ -469,9 +473,13 @@ int pk_network_simulate_measure_batch(pk_ctx*, pk_net*, pk_loss* lists, int64_t 
  *   repeated one is PK_ERR_ARG.  dY [B,T,S,K], the K derivatives of one state at one time contiguous; row t = 0 of dY is 0.  Y [B,T,S] | NULL.
  *   With x_is_raw the derivative is with respect to the RAW entry: the physical derivative times softplus'(raw), exactly 1 where softplus
  *   returns its argument (raw > 20).  x, y0, Y, dY, status, n_steps: DEVICE pointers; t, cols: HOST.
- * Always PK_METHOD_ROS34PW2 on the general LDS kernel, whatever opts->method / linsolve say -- except that an explicit PK_METHOD_ARK436,
- * PK_METHOD_DP5 or PK_KERNEL_WORKSPACE is PK_ERR_UNSUPPORTED (pk_last_error names the remedy), as is a network on which not one column
- * fits beside the state in 160 KiB of LDS or that is beyond the LDS kernel (S > 1024, N > 512): the workspace kernel carries no tangents.
+ * Always PK_METHOD_ROS34PW2, whatever opts->method / linsolve say -- except that an explicit PK_METHOD_ARK436, PK_METHOD_DP5 or
+ * PK_KERNEL_WORKSPACE is PK_ERR_UNSUPPORTED (pk_last_error names the remedy).  Route: the general LDS kernel where at least one column fits
+ * beside the state in 160 KiB of LDS (pk_network_sens_columns_per_launch >= 1); the slab route -- state and tangents in slabs of the
+ * context's scratch arena, no size limit but device memory -- on every other network (S > 1024, N > 512, or no column fits) and, at any
+ * size, with opts->kernel = PK_KERNEL_HBM.  On slabs KC = pk_network_sens_hbm_columns, the launch is a persistent grid of
+ * min(B x ceil(K / KC), resident workgroups) over the (candidate, chunk) items, and pk_network_sens_workspace_bytes reports the slabs; every
+ * rule below holds on both routes, and a candidate's numbers agree between them within rounding, not bit for bit.
  * Tangents are held to the same rtol / atol as the states, in the norm opts->err_norm selects (maximum over states and columns; RMS: over
  * all S (1 + columns of the workgroup) entries).
  * Column chunks: one workgroup integrates one candidate with up to KC = pk_network_sens_columns_per_launch columns, the launch is
@@ -480,14 +488,24 @@ int pk_network_simulate_measure_batch(pk_ctx*, pk_net*, pk_loss* lists, int64_t 
  * Failure: a flagged chunk leaves NaN in its own columns at the rows it did not reach, and in every row when it is PK_ST_NONFINITE (a
  * non-finite state, parameter or tangent, or a tangent beyond 1e100 in magnitude, at a step whose error is not finite); Y follows
  * pk_network_simulate_batch's rule.
- * K = 0 with Y set is pk_network_simulate_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED, bit for bit; B = 0 is PK_OK; dY NULL
- * with K > 0 is PK_ERR_ARG.  A candidate's results do not depend on the batch around it. */
+ * K = 0 with Y set is pk_network_simulate_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED, bit for bit (with PK_KERNEL_HBM: with
+ * PK_KERNEL_WORKSPACE); B = 0 is PK_OK; dY NULL with K > 0 is PK_ERR_ARG.  A candidate's results do not depend on the batch around it. */
 int pk_network_simulate_sens_batch(pk_ctx*, pk_net*, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                                    const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host, int K,
                                    double* Y, double* dY, int32_t* status, int32_t* n_steps);
 /* KC of pk_network_simulate_sens_batch on this network: the largest column count whose LDS request stays within 160 KiB (at most n_var);
- * 0 = not one column fits.  Pure host arithmetic. */
+ * 0 = not one column fits or the network is beyond the LDS kernel (the slab route then runs).  Pure host arithmetic. */
 int pk_network_sens_columns_per_launch(pk_net*);
+/* KC of the slab route for a request of K columns: min(K, n_var, W) with W = 16 -- not bound by LDS; the dev knob PK_NET_SENS_KC lowers W
+ * as it lowers the LDS counts.  scoring: 0 = pk_network_simulate_sens_batch, 1 = pk_network_simulate_objective_grad_batch (the same width
+ * today).  PK_ERR_ARG for a null handle or K < 0.  Pure host arithmetic. */
+int pk_network_sens_hbm_columns(pk_net*, int K, int scoring);
+/* Bytes of slabs the slab route reserves in the context's scratch arena for B candidates and K columns (1 <= K <= n_var): grid x slab, grid =
+ * min(B x ceil(K / KC), workgroups of the flavour's kernel resident on the context's GPU) -- bounded in B --, slab = the plain work area of
+ * pk_network_workspace_bytes plus the sensitivity area the LDS kernels keep behind the plain request (2 N + KC (7 S + total_sites + N + 2)
+ * doubles; scoring: N + 4 + KC (N + 3) more), rounded up to 128 B.  The K column indices are staged in front of the slabs (4 K bytes in
+ * whole 128-B lines, not counted here).  < 0 on error. */
+int64_t pk_network_sens_workspace_bytes(pk_ctx*, pk_net*, int64_t B, int K, int scoring);
 
 /* The three objectives of pk_network_simulate_objective_batch AND their exact discrete derivative with respect to K chosen entries
  * cols[k] of the candidate vector, from ONE launch: the sensitivity integrator above differentiates the loss where the state and the
@@ -498,9 +516,10 @@ int pk_network_sens_columns_per_launch(pk_net*);
  *   (protein | rna | phospho) list order), loss_sums [B,3] and dsums [B,3,K] (the weighted sums and their derivative),
  *   F [B,3] and dF [B,3,K] = dsums norm_m lambda_m + d prior / d x_c; the prior term lambda_prior 2 (p - d) / (d + 1e-6)^2 / (5 N) is non-zero
  *   for columns in A, B, C, D, E and enters all three objectives.  With x_is_raw every derivative is with respect to the raw entry.
- * Rules of pk_network_simulate_sens_batch: always PK_METHOD_ROS34PW2 on the general LDS kernel; an explicit PK_METHOD_ARK436,
+ * Rules of pk_network_simulate_sens_batch: always PK_METHOD_ROS34PW2, on the general LDS kernel where
+ * pk_network_objective_grad_columns_per_launch >= 1 and on HBM slabs elsewhere or with PK_KERNEL_HBM; an explicit PK_METHOD_ARK436,
  * PK_METHOD_DP5 or PK_KERNEL_WORKSPACE is PK_ERR_UNSUPPORTED; cols (HOST) is checked on the host; column chunks of
- * KC = pk_network_objective_grad_columns_per_launch, each integrating the state itself; chunk 0 writes Y, pred, loss_sums, F and n_steps;
+ * KC = pk_network_objective_grad_columns_per_launch (slabs: pk_network_sens_hbm_columns), each integrating the state itself; chunk 0 writes Y, pred, loss_sums, F and n_steps;
  * status is the OR over the chunks.  Rules of the order-3 fused objective: protein / phospho baselines are time index 0 and no rna
  * observation lies before the rna baseline (else PK_ERR_UNSUPPORTED); a (state, time) may be observed twice; loss_mode 0..7; T equals the
  * handle's; lambdas is required for F / dF.  PK_ERR_ARG when every output pointer is NULL, or K > 0 and dY, dpred, dsums, dF are all NULL.
@@ -508,8 +527,8 @@ int pk_network_sens_columns_per_launch(pk_net*);
  * permuting cols permutes the outputs (K <= KC, maximum norm).
  * Failure: a flagged chunk has NaN in its own columns of dsums, dF and dpred; F = fail_value and an all-NaN pred row when chunk 0 is
  * flagged or a state of a scored row is not finite.
- * K = 0 is pk_network_simulate_objective_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED, bit for bit (loss_sums or F required,
- * pred must be NULL).  pk_last_error names the remedy for every refusal. */
+ * K = 0 is pk_network_simulate_objective_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED, bit for bit (with PK_KERNEL_HBM: with
+ * PK_KERNEL_WORKSPACE; loss_sums or F required, pred must be NULL).  pk_last_error names the remedy for every refusal. */
 int pk_network_simulate_objective_grad_batch(pk_ctx*, pk_net*, pk_loss*, int64_t B, const double* x, int x_is_raw, const double* y0,
                                              int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts,
                                              const int32_t* cols_host, int K, int loss_mode, const double* defaults, const double* lambdas,

@@ -19,8 +19,8 @@ METHOD_RODAS4, METHOD_BDF2, METHOD_RK4, METHOD_LRP8, METHOD_DP5, METHOD_LRP12, M
 METHODS = {"rodas4": METHOD_RODAS4, "bdf2": METHOD_BDF2, "rk4": METHOD_RK4, "lrp8": METHOD_LRP8, "dp5": METHOD_DP5, "lrp12": METHOD_LRP12, "ark436": METHOD_ARK436, "ros34pw2": METHOD_ROS34PW2}
 LINSOLVE_AUTO, LINSOLVE_DENSE, LINSOLVE_STRUCTURED = 0, 1, 2
 LINSOLVES = {"auto": LINSOLVE_AUTO, "dense": LINSOLVE_DENSE, "structured": LINSOLVE_STRUCTURED}
-KERNEL_AUTO, KERNEL_GROUP, KERNEL_TPR, KERNEL_WORKSPACE = 0, 1, 2, 3
-KERNELS = {"auto": KERNEL_AUTO, "group": KERNEL_GROUP, "tpr": KERNEL_TPR, "workspace": KERNEL_WORKSPACE}
+KERNEL_AUTO, KERNEL_GROUP, KERNEL_TPR, KERNEL_WORKSPACE, KERNEL_HBM = 0, 1, 2, 3, 4
+KERNELS = {"auto": KERNEL_AUTO, "group": KERNEL_GROUP, "tpr": KERNEL_TPR, "workspace": KERNEL_WORKSPACE, "hbm": KERNEL_HBM}
 NORMS = {"default": 0, "max": 1, "rms": 2}
 METRICS = {"total_signal": 0, "mean_activity": 1, "variance": 2, "dynamics": 3, "l2_norm": 4}
 ST_NONFINITE, ST_MAXSTEPS, ST_HMIN = 1, 2, 4
@@ -78,6 +78,7 @@ SYMBOLS = (
     "pk_network_loss_create", "pk_network_loss_destroy", "pk_network_objective_batch", "pk_network_simulate_objective_batch", "pk_network_observables_batch", "pk_network_simulate_measure_batch", "pk_frechet_batch", "pk_loss_fn_batch_host", "pk_network_resolve_method",
     "pk_network_workspace_bytes", "pk_network_simulate_sens_batch", "pk_network_sens_columns_per_launch",
     "pk_network_simulate_objective_grad_batch", "pk_network_objective_grad_columns_per_launch",
+    "pk_network_sens_hbm_columns", "pk_network_sens_workspace_bytes",
     "pk_comm_unique_id", "pk_comm_init", "pk_comm_rank", "pk_comm_world", "pk_allgather_f64", "pk_comm_destroy",
 )
 
@@ -168,6 +169,8 @@ def load():
     lib.pk_network_simulate_objective_grad_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, optp, vp, i32, i32, vp, vp, dbl,
                                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.pk_network_objective_grad_columns_per_launch.restype = i32; lib.pk_network_objective_grad_columns_per_launch.argtypes = [vp]
+    lib.pk_network_sens_hbm_columns.restype = i32; lib.pk_network_sens_hbm_columns.argtypes = [vp, i32, i32]
+    lib.pk_network_sens_workspace_bytes.restype = i64; lib.pk_network_sens_workspace_bytes.argtypes = [vp, vp, i64, i32, i32]
     lib.pk_network_resolve_method.restype = i32; lib.pk_network_resolve_method.argtypes = [vp, optp]
     lib.pk_network_workspace_bytes.restype = i64; lib.pk_network_workspace_bytes.argtypes = [vp, vp, i64]
     lib.pk_loss_fn_batch_host.restype = i32

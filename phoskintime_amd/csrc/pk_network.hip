@@ -30,6 +30,10 @@ hipError_t launch_net_lds_sens(const NetDev& n, const NetSolveArgs& a, const Net
 // ... and scoring the loss and its gradient from those tangents as they land (pk_inst_net_rosw_sens_score.hip)
 hipError_t launch_net_lds_sens_score(const NetDev& n, const NetSolveArgs& a, const NetSensArgs& s, const NetSensScoreArgs& sc, long long B, int threads,
                                      size_t lds, hipStream_t st);
+// ... and the same two flavours on HBM-workspace slabs, a persistent grid over (candidate, column chunk) items (pk_inst_net_rosw_sens_ws.hip)
+hipError_t net_sens_ws_grid(const NetDev& n, bool score, long long items, int* grid);
+hipError_t launch_net_ws_sens(const NetDev& n, const NetSolveArgs& a, const NetSensArgs& s, const NetSensScoreArgs* sc, long long B, int grid,
+                              double* ws, hipStream_t st);
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
@@ -313,7 +317,8 @@ int pk_network_jacobian_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, 
 // is the default (or was asked for); otherwise PK_METHOD_ROS34PW2.  ROS34PW2 always runs on the workspace kernel for networks beyond the
 // one-workgroup LDS kernels (S > 1024, N > 512, or more than 160 KiB of LDS for the general one; small combinatorial blocks run out of
 // registers and are exempt) and on request (opts->kernel = PK_KERNEL_WORKSPACE).  A refused plan has code PK_ERR_UNSUPPORTED and a
-// message; its method is then PK_ERR_UNSUPPORTED, except for a DP5 request on a network too large for the DP5 kernel.
+// message; its method is then PK_ERR_UNSUPPORTED, except for a DP5 request on a network too large for the DP5 kernel.  PK_KERNEL_HBM is
+// read by the two sensitivity entry points alone (they translate it before they plan): every other caller of this plan is refused.
 enum class NetKernel { DP5, Workspace, ArkPair, Ark, CombReg, Reg, Lds };
 struct NetPlan {
   int method;
@@ -331,6 +336,9 @@ static NetPlan net_plan(const pk_net* n, const pk_solver_opts* opts) {
   const int threads = ((d.N + 63) / 64) * 64;
   auto take = [&](int m, NetKernel k) { return NetPlan{m, k, PK_OK, nullptr, threads}; };
   auto refuse = [&](int m, const char* why) { return NetPlan{m, NetKernel::Lds, PK_ERR_UNSUPPORTED, why, threads}; };
+  if (opts && opts->kernel == PK_KERNEL_HBM)
+    return refuse(PK_ERR_UNSUPPORTED, "PK_KERNEL_HBM is read by pk_network_simulate_sens_batch and pk_network_simulate_objective_grad_batch only; "
+                                      "ask for PK_KERNEL_WORKSPACE here");
   if (method == PK_METHOD_DP5) {
     if (ws_forced) return refuse(PK_ERR_UNSUPPORTED, "PK_KERNEL_WORKSPACE integrates with PK_METHOD_ROS34PW2 only");
     if (d.S > 1024 || d.N > 512) return refuse(PK_METHOD_DP5, "PK_METHOD_DP5: S <= 1024 states and N <= 512 proteins per network");
@@ -369,9 +377,10 @@ int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { ret
 // fused->loss_ptr set (the time-bucketed lists: the caller asked for the order-3 method or the workspace kernel) the launch runs where the
 // plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel.  fused->meas: the same lists measured
 // instead of scored (pk_network_simulate_measure_batch), on the same two kernels.  `sens`: null, or the columns of
-// pk_network_simulate_sens_batch (cols: HOST pointer; Y may then be null): the plan must be the general LDS kernel.  sens->score: the
-// scoring flavour (pk_network_simulate_objective_grad_batch); `fused` then carries the loss lists, the permutation and the loss outputs
-struct NetSensReq { const int32_t* cols_host; int K, KC; double* dY; const pk::NetSensScoreArgs* score = nullptr; };
+// pk_network_simulate_sens_batch (cols: HOST pointer; Y may then be null): the plan must be the general LDS kernel, or with sens->hbm the
+// workspace kernel (the tangents on slabs).  sens->score: the scoring flavour (pk_network_simulate_objective_grad_batch); `fused` then
+// carries the loss lists, the permutation and the loss outputs
+struct NetSensReq { const int32_t* cols_host; int K, KC; double* dY; const pk::NetSensScoreArgs* score = nullptr; bool hbm = false; };
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                              const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps,
                              const pk::NetSolveArgs* fused, const NetSensReq* sens = nullptr) {
@@ -384,9 +393,9 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   if (n->d.model == 2 && n->max_sites > 16) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "combinatorial topology: <= 16 sites per protein");
   NetPlan plan = net_plan(n, opts_in);
   if (plan.code != PK_OK) return pk_ctx_fail(c, plan.code, plan.refusal);
-  if (sens && plan.kernel != NetKernel::Lds)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: the general LDS kernel only (S <= 1024, N <= 512, 160 KiB of LDS); the "
-                                              "HBM-workspace kernel carries no tangents: difference pk_network_simulate_batch there");
+  if (sens && plan.kernel != (sens->hbm ? NetKernel::Workspace : NetKernel::Lds))
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: the plan for these options is neither the general LDS kernel nor the "
+                                              "HBM-workspace kernel");
   const bool rosw_fused = fused && fused->loss_ptr && !sens;
   const bool measure = rosw_fused && fused->meas;
   if (measure) {
@@ -473,6 +482,26 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
   const int M = n->d.model;
   switch (plan.kernel) {
     case NetKernel::Workspace: {
+      if (sens) {
+        // tangents on slabs: a persistent grid over the B x ceil(K / KC) (candidate, chunk) items.  The scratch arena holds the column
+        // indices (whole 128-B lines) and behind them grid x slab; status is OR-ed over the chunks, so it is zeroed first
+        const int kcl = std::min(sens->K, sens->KC), n_chunks = (sens->K + sens->KC - 1) / sens->KC;
+        const size_t cols_bytes = ((size_t)sens->K * sizeof(int32_t) + 127) / 128 * 128;
+        struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; const NetSensReq* s; long long B; int grid; size_t cols_bytes; int32_t* status; }
+            q{&n->d, &a, sens, (long long)B, 0, cols_bytes, status};
+        if (pk::net_sens_ws_grid(n->d, sens->score != nullptr, (long long)B * n_chunks, &q.grid) != hipSuccess)
+          return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+        auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
+          const Q& r = *(const Q*)user;
+          hipError_t e = hipMemcpyAsync(scratch, r.s->cols_host, (size_t)r.s->K * sizeof(int32_t), hipMemcpyHostToDevice, s);
+          if (e == hipSuccess && r.status) e = hipMemsetAsync(r.status, 0, (size_t)r.B * sizeof(int32_t), s);
+          if (e != hipSuccess) return e;
+          const pk::NetSensArgs sa{(const int32_t*)scratch, r.s->K, r.s->KC, r.s->dY};
+          return pk::launch_net_ws_sens(*r.d, *r.a, sa, r.s->score, r.B, r.grid, (double*)((char*)scratch + r.cols_bytes), s);
+        };
+        const size_t slab = pk::net_sens_ws_slab_doubles(n->d, kcl, sens->score != nullptr);
+        return pk_ctx_scratch_launch(c, cols_bytes + (size_t)q.grid * slab * sizeof(double), launch, &q);
+      }
       // ROS34PW2 on workspace slabs (net_solve_ws_kernel): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
       struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; bool fused, measure; } q{&n->d, &a, (long long)B, 0, rosw_fused, measure};
       if ((measure ? pk::net_ws_measure_grid(n->d, (long long)B, &q.grid) : rosw_fused ? pk::net_ws_fused_grid(n->d, (long long)B, &q.grid)
@@ -664,8 +693,34 @@ int pk_network_sens_columns_per_launch(pk_net* n) {
   return kc;
 }
 
-// Y and dY / dx[cols] from one integration of the augmented system (pk_network_sens.hpp).  Always the order-3 method on the general LDS
-// kernel; K = 0 is pk_network_simulate_batch on that kernel
+// Columns one work item of the slab route carries: min(K, n_var, W), W = 16 (DESIGN 5.9 records the measurement behind it); the dev knob
+// PK_NET_SENS_KC lowers W as it lowers the LDS counts (read at every call).  The width is the same for both flavours: `scoring` is part of
+// the signature so that it may differ one day.  Host arithmetic only
+int pk_network_sens_hbm_columns(pk_net* n, int K, int scoring) {
+  if (!n || K < 0) return PK_ERR_ARG;
+  (void)scoring;
+  int W = 16;
+  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < W) W = v; }
+  return std::min(std::min(K, n->d.n_var), W);
+}
+
+// Bytes of slabs a launch of the slab route reserves: grid x slab, grid = min(B x chunks, resident workgroups of the flavour's kernel) -- bounded
+// in B.  (The launch stages the K column indices in front of the slabs: 4 K bytes, in whole 128-B lines, on top of this figure)
+int64_t pk_network_sens_workspace_bytes(pk_ctx* c, pk_net* n, int64_t B, int K, int scoring) {
+  if (!c || !n) return PK_ERR_ARG;
+  if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
+  if (K < 1 || K > n->d.n_var) return pk_ctx_fail(c, PK_ERR_ARG, "K must be in [1, n_var]");
+  if (B > 0x7fffffffLL) return pk_ctx_fail(c, PK_ERR_ARG, "batch too large for one launch");
+  if (hipSetDevice(pk_ctx_device(c)) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipSetDevice");
+  const int kc = pk_network_sens_hbm_columns(n, K, scoring), n_chunks = (K + kc - 1) / kc;
+  int grid = 0;
+  if (pk::net_sens_ws_grid(n->d, scoring != 0, (long long)B * n_chunks, &grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+  return (int64_t)grid * (int64_t)(pk::net_sens_ws_slab_doubles(n->d, kc, scoring != 0) * sizeof(double));
+}
+
+// Y and dY / dx[cols] from one integration of the augmented system (pk_network_sens.hpp).  Always the order-3 method: on the general LDS
+// kernel where a column fits beside the state, else -- and with PK_KERNEL_HBM -- on HBM slabs.  K = 0 is pk_network_simulate_batch on the
+// general LDS kernel (PK_KERNEL_HBM: on the workspace kernel)
 int pk_network_simulate_sens_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                                    const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host, int K, double* Y,
                                    double* dY, int32_t* status, int32_t* n_steps) {
@@ -676,7 +731,8 @@ int pk_network_simulate_sens_batch(pk_ctx* c, pk_net* n, int64_t B, const double
     return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities integrate with PK_METHOD_ROS34PW2 only: leave opts->method at its default or ask for "
                                               "PK_METHOD_ROS34PW2");
   if (opts && opts->kernel == PK_KERNEL_WORKSPACE)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities run on the general LDS kernel only: leave opts->kernel at PK_KERNEL_AUTO");
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: PK_KERNEL_WORKSPACE names the state kernel; leave opts->kernel at PK_KERNEL_AUTO, or "
+                                              "ask for the tangents on HBM slabs with PK_KERNEL_HBM");
   if (K > 0) {
     if (!cols_host) return pk_ctx_fail(c, PK_ERR_ARG, "cols is NULL with K > 0");
     if (!dY) return pk_ctx_fail(c, PK_ERR_ARG, "dY is NULL with K > 0");
@@ -691,13 +747,14 @@ int pk_network_simulate_sens_batch(pk_ctx* c, pk_net* n, int64_t B, const double
   if (B == 0) return PK_OK;
   pk_solver_opts o;
   if (opts) o = *opts; else pk_default_opts(&o);
-  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = PK_KERNEL_AUTO;
+  const bool hbm_asked = o.kernel == PK_KERNEL_HBM;
+  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = hbm_asked ? PK_KERNEL_WORKSPACE : PK_KERNEL_AUTO;
   if (K == 0) return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr);
-  const int KC = pk_network_sens_columns_per_launch(n);
-  if (KC < 1)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: not one tangent column fits beside the state in one workgroup's LDS (160 KiB) on this "
-                                              "network, or it is beyond the LDS kernel (S <= 1024, N <= 512); difference pk_network_simulate_batch");
-  const NetSensReq req{cols_host, K, KC, dY};
+  // the LDS kernel where a column fits beside the state; the slabs on request and wherever it does not
+  int KC = hbm_asked ? 0 : pk_network_sens_columns_per_launch(n);
+  const bool hbm = KC < 1;
+  if (hbm) { KC = pk_network_sens_hbm_columns(n, K, 0); o.kernel = PK_KERNEL_WORKSPACE; }
+  const NetSensReq req{cols_host, K, KC, dY, nullptr, hbm};
   return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr, &req);
 }
 
@@ -713,9 +770,9 @@ int pk_network_objective_grad_columns_per_launch(pk_net* n) {
 
 // The three objectives AND their derivative with respect to x[cols] from one integration of the augmented system: the scoring flavour of
 // the sensitivity kernel differentiates the loss where state and tangents land on an output row (pk_network_sens.hpp); neither the
-// trajectory nor the tangent trajectory reaches HBM unless Y / dY are asked for.  Rules of pk_network_simulate_sens_batch (order-3 method,
-// general LDS kernel, cols checked here) and of the order-3 fused objective (the time-bucketed lists).  K = 0 is
-// pk_network_simulate_objective_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED
+// trajectory nor the tangent trajectory reaches HBM as an output unless Y / dY are asked for.  Rules of pk_network_simulate_sens_batch (order-3
+// method, general LDS kernel or HBM slabs, cols checked here) and of the order-3 fused objective (the time-bucketed lists).  K = 0 is
+// pk_network_simulate_objective_batch with PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED (PK_KERNEL_HBM: with PK_KERNEL_WORKSPACE)
 int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_t B, const double* x, int x_is_raw, const double* y0,
                                              int y0_is_batched, const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host,
                                              int K, int loss_mode, const double* defaults, const double* lambdas, double fail_value, double* Y,
@@ -728,8 +785,8 @@ int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, i
     return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients integrate with PK_METHOD_ROS34PW2 only: leave opts->method at its default or ask for "
                                               "PK_METHOD_ROS34PW2");
   if (opts && opts->kernel == PK_KERNEL_WORKSPACE)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients run on the general LDS kernel only (the workspace kernel carries no tangents): leave "
-                                              "opts->kernel at PK_KERNEL_AUTO");
+    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients: PK_KERNEL_WORKSPACE names the state kernel; leave opts->kernel at PK_KERNEL_AUTO, or "
+                                              "ask for the tangents on HBM slabs with PK_KERNEL_HBM");
   if (loss_mode < 0 || loss_mode > 7) return pk_ctx_fail(c, PK_ERR_ARG, "loss_mode must be 0..7");
   if (!Y && !dY && !pred && !dpred && !loss_sums && !dsums && !F && !dF)
     return pk_ctx_fail(c, PK_ERR_ARG, "every output pointer is NULL: pass at least one of Y, dY, pred, dpred, loss_sums, dsums, F, dF");
@@ -748,7 +805,8 @@ int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, i
   }
   pk_solver_opts o;
   if (opts) o = *opts; else pk_default_opts(&o);
-  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = PK_KERNEL_AUTO;
+  const bool hbm_asked = o.kernel == PK_KERNEL_HBM;
+  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = hbm_asked ? PK_KERNEL_WORKSPACE : PK_KERNEL_AUTO;
   if (K == 0) {
     if (pred || (!loss_sums && !F))
       return pk_ctx_fail(c, PK_ERR_ARG, "K = 0 computes loss_sums / F (and Y) as pk_network_simulate_objective_batch does: pass one of them, and ask "
@@ -766,16 +824,15 @@ int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, i
                                               "than the rna baseline; difference pk_network_simulate_batch + pk_network_objective_batch");
   if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the loss data were created for");
   if (B == 0) return PK_OK;
-  const int KC = pk_network_objective_grad_columns_per_launch(n);
-  if (KC < 1)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients: not one tangent column fits beside the state in one workgroup's LDS (160 KiB) on this "
-                                              "network, or it is beyond the LDS kernel (S <= 1024, N <= 512); difference pk_network_simulate_objective_batch");
+  int KC = hbm_asked ? 0 : pk_network_objective_grad_columns_per_launch(n);
+  const bool hbm = KC < 1;
+  if (hbm) { KC = pk_network_sens_hbm_columns(n, K, 1); o.kernel = PK_KERNEL_WORKSPACE; }
   f.loss_defaults = defaults; f.loss_mode = loss_mode; f.loss_fail = fail_value; f.loss_sums = loss_sums; f.loss_F = F;
   f.loss_lam[0] = lambdas ? lambdas[0] : 1.0; f.loss_lam[1] = lambdas ? lambdas[1] : 1.0; f.loss_lam[2] = lambdas ? lambdas[2] : 1.0;
   f.loss_lam[3] = lambdas ? lambdas[3] : 0.0;
   f.meas_pred = pred;
   const pk::NetSensScoreArgs sc{dpred, dsums, dF};
-  const NetSensReq req{cols_host, K, KC, dY, &sc};
+  const NetSensReq req{cols_host, K, KC, dY, &sc, hbm};
   return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, &f, &req);
 }
 

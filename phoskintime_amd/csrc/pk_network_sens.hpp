@@ -690,4 +690,53 @@ __global__ __launch_bounds__(256) void net_solve_sens_score_kernel(const NetDev 
                                          lds + net_solve_lds_bytes(n, nnzT) / 8);
 }
 
+// ---- Networks of any size: the same body with every per-item vector in a slab of an HBM workspace (as net_solve_ws_kernel runs
+// net_rosw_solve).  A slab is the plain work area (net_rosw_doubles) followed by the sensitivity area of kc columns -- exactly the doubles
+// the LDS kernels place behind the plain request, so the column arithmetic has one source (the nnzT terms cancel in the difference) --
+// rounded up to whole 128-B lines.  The chunk width is not bound by LDS
+__host__ __device__ inline size_t net_sens_ws_slab_doubles(const NetDev& n, int kc, bool score) {
+  const size_t area = ((score ? net_sens_score_lds_bytes(n, 0, kc) : net_sens_lds_bytes(n, 0, kc)) - net_solve_lds_bytes(n, 0)) / 8;
+  return (net_rosw_doubles(n) + area + 15) / 16 * 16;
+}
+
+// Persistent grid over work items: item w = b * n_chunks + j is candidate b with the columns [j KC, j KC + kc) of SA.cols; workgroup g takes
+// w = g, g + grid, ...  LDS holds only the reduction buffer; the TF CSR is read from global memory (NetWsLayout).  Visibility inside a
+// workgroup: the body's __syncthreads() (workgroup-scope release / acquire), as in net_solve_ws_kernel; no workgroup reads another's slab,
+// and every accumulator slot of the scoring flavour stays one thread's.  The body re-initialises what an item leaves behind (parameters,
+// column table, tangents, accumulators; the rna baseline is written at its row before any entry reads it).  status: the chunks of one
+// candidate may run in different workgroups and rounds -- the body's atomicOr on status[b] (device scope) forms the OR whatever the order,
+// the host zeroes status before the launch
+template <int MODEL>
+__global__ __launch_bounds__(256) void net_solve_sens_ws_kernel(const NetDev n, const NetSolveArgs A, const NetSensArgs SA, const long long items,
+                                                                const int n_chunks, double* __restrict__ ws, const size_t slab) {
+  __shared__ double red[24];
+  double* const base0 = ws + (size_t)blockIdx.x * slab;
+  const NetWsLayout lay(n);
+  for (long long w = blockIdx.x; w < items; w += gridDim.x) {
+    __syncthreads();                                   // the previous item of this workgroup is done with the slab
+    const long long b = w / n_chunks;
+    const int c0 = (int)(w - b * n_chunks) * SA.KC;
+    const int kc = min(SA.KC, SA.K - c0);
+    net_rosw_sens_solve<MODEL, SENS_STORE>(n, A, SA, nullptr, lay, b, c0, kc, NetLds(base0, n), base0 + NetLds::doubles(n), red,
+                                           base0 + net_rosw_doubles(n));
+  }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void net_solve_sens_score_ws_kernel(const NetDev n, const NetSolveArgs A, const NetSensArgs SA,
+                                                                      const NetSensScoreArgs SC, const long long items, const int n_chunks,
+                                                                      double* __restrict__ ws, const size_t slab) {
+  __shared__ double red[24];
+  double* const base0 = ws + (size_t)blockIdx.x * slab;
+  const NetWsLayout lay(n);
+  for (long long w = blockIdx.x; w < items; w += gridDim.x) {
+    __syncthreads();                                   // the previous item of this workgroup is done with the slab (rna baseline, accumulators)
+    const long long b = w / n_chunks;
+    const int c0 = (int)(w - b * n_chunks) * SA.KC;
+    const int kc = min(SA.KC, SA.K - c0);
+    net_rosw_sens_solve<MODEL, SENS_SCORE>(n, A, SA, &SC, lay, b, c0, kc, NetLds(base0, n), base0 + NetLds::doubles(n), red,
+                                           base0 + net_rosw_doubles(n));
+  }
+}
+
 }  // namespace pk

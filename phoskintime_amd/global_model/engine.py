@@ -309,6 +309,22 @@ class NetworkEngine:
         arithmetic on the LDS budget); 0 when not even one fits."""
         return int(_capi.load().pk_network_sens_columns_per_launch(self._h))
 
+    def sens_hbm_columns(self, K: int, scoring: bool = False) -> int:
+        """Tangent columns one work item of the slab route carries for a request of ``K`` columns (``pk_network_sens_hbm_columns``:
+        min(K, n_var, 16); not bound by LDS).  ``scoring``: the width of ``simulate_objective_grad_batch``."""
+        v = int(_capi.load().pk_network_sens_hbm_columns(self._h, int(K), int(bool(scoring))))
+        if v < 0:
+            raise ValueError("K must be >= 0")
+        return v
+
+    def sens_workspace_bytes(self, B: int, K: int, scoring: bool = False) -> int:
+        """HBM the slab route of ``simulate_sens_batch`` (``scoring``: of ``simulate_objective_grad_batch``) takes from the context's scratch
+        arena for B candidates and K columns (``pk_network_sens_workspace_bytes``): min(B x chunks, resident workgroups) slabs, bounded in B."""
+        v = int(self.ctx.lib.pk_network_sens_workspace_bytes(self.ctx.handle, self._h, int(B), int(K), int(bool(scoring))))
+        if v < 0:
+            self.ctx.check(v)
+        return v
+
     def simulate_sens_batch(self, x, t_eval, cols, y0=None, raw: bool = False, rtol: Optional[float] = None, atol: Optional[float] = None,
                             max_steps: int = 1000000, want_Y: bool = True, method: str = "auto", kernel: str = "auto", err_norm: str = "max"):
         """The trajectory AND its derivative with respect to the entries ``cols`` of the candidate vector (indices into ``x``, in
@@ -316,17 +332,18 @@ class NetworkEngine:
         (``pk_network_simulate_sens_batch``, csrc/pk_network_sens.hpp).  Returns (dY [B, T, S, K], Y [B, T, S] or None, status [B],
         n_steps [B, 2]) as GPU tensors; ``dY[:, 0]`` is 0 (``y0`` is data).  ``raw=True``: ``x`` holds raw entries and the derivative is
         with respect to them (physical derivative times softplus').  Default tolerances are the order-3 kernel's, 1e-7 / 1e-9, as in
-        ``simulate_measure_batch``; tangents are held to the same tolerances as the states.  The launch always runs the order-3 method on
-        the general LDS kernel, ``sens_columns_per_launch()`` columns per workgroup, each chunk of columns integrating the state itself:
-        ``status`` is the OR over the chunks, ``n_steps`` is chunk 0's.  A flagged candidate has NaN in the columns of the flagged chunk
-        at the rows it did not reach.  ``None`` when the launch is refused (PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy):
-        ``method`` "ark" / "dp5", ``kernel="workspace"``, or a network on which no column fits in one workgroup's LDS.  This is a tool for
+        ``simulate_measure_batch``; tangents are held to the same tolerances as the states.  The launch always runs the order-3 method:
+        on the general LDS kernel, ``sens_columns_per_launch()`` columns per workgroup, where at least one column fits beside the state;
+        on HBM slabs, ``sens_hbm_columns(K)`` columns per work item, on every other network (any size) and with ``kernel="hbm"``.  Each
+        chunk of columns integrates the state itself: ``status`` is the OR over the chunks, ``n_steps`` is chunk 0's.  A flagged candidate
+        has NaN in the columns of the flagged chunk at the rows it did not reach.  ``None`` when the launch is refused
+        (PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy): ``method`` "ark" / "dp5" or ``kernel="workspace"``.  This is a tool for
         the local sensitivity of a chosen handful of parameters -- per column about (1 + KC) / KC state integrations against 2 for central
         differences --, not a full gradient."""
         if method not in ("auto", "ark", "rosw", "dp5"):
             raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
-        if kernel not in ("auto", "lds", "workspace"):
-            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
+        if kernel not in ("auto", "lds", "workspace", "hbm"):
+            raise ValueError("kernel must be 'auto', 'lds', 'workspace' or 'hbm'")
         rtol = 1e-7 if rtol is None else rtol
         atol = 1e-9 if atol is None else atol
         dev = torch.device("cuda", self.ctx.device)
@@ -378,16 +395,18 @@ class NetworkEngine:
         HBM unless asked for.  Returns a dict of GPU tensors -- ``status`` [B], ``n_steps`` [B, 2], and as asked: ``F`` [B, 3] and ``dF``
         [B, 3, K] (``want_F``), ``loss_sums`` [B, 3] and ``dsums`` [B, 3, K] (``want_sums``), ``pred`` [B, n_obs] and ``dpred``
         [B, n_obs, K] in the order of the lists as given (``want_pred``), ``Y`` (``want_Y``), ``dY`` (``want_dY``) -- or ``None`` when the
-        launch is refused (PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy): ``method`` "ark" / "dp5", ``kernel="workspace"``, an
-        rna observation before the rna baseline, or a network on which no column fits.  ``raw=True``: derivatives with respect to the raw
-        entries.  Tolerances default to the order-3 kernel's 1e-7 / 1e-9.  ``objective_grad_columns_per_launch()`` columns share one
-        workgroup; every chunk of columns integrates the state itself.  A candidate's numbers are bit-equal alone and in any batch.  With
-        no columns the call is ``simulate_objective_batch(method="rosw", kernel="lds")``.  A full gradient over all ``n_var`` columns
-        costs n_var / KC state integrations: this is a tool for a gradient polish or a Gauss-Newton step on chosen parameters."""
+        launch is refused (PK_ERR_UNSUPPORTED; ``pk_last_error`` names the remedy): ``method`` "ark" / "dp5", ``kernel="workspace"`` or an
+        rna observation before the rna baseline.  ``raw=True``: derivatives with respect to the raw entries.  Tolerances default to the
+        order-3 kernel's 1e-7 / 1e-9.  ``objective_grad_columns_per_launch()`` columns share one workgroup of the LDS kernel; where not one
+        fits (a network of any size) and with ``kernel="hbm"`` the launch runs on HBM slabs, ``sens_hbm_columns(K, scoring=True)`` columns
+        per work item.  Every chunk of columns integrates the state itself.  A candidate's numbers are bit-equal alone and in any batch.
+        With no columns the call is ``simulate_objective_batch(method="rosw", kernel="lds")`` (``kernel="hbm"``: ``kernel="workspace"``).
+        A full gradient over all ``n_var`` columns costs n_var / KC state integrations: this is a tool for a gradient polish or a
+        Gauss-Newton step on chosen parameters."""
         if method not in ("auto", "ark", "rosw", "dp5"):
             raise ValueError("method must be 'auto', 'ark', 'rosw' or 'dp5'")
-        if kernel not in ("auto", "lds", "workspace"):
-            raise ValueError("kernel must be 'auto', 'lds' or 'workspace'")
+        if kernel not in ("auto", "lds", "workspace", "hbm"):
+            raise ValueError("kernel must be 'auto', 'lds', 'workspace' or 'hbm'")
         if loss not in self._n_obs:
             raise ValueError("loss must be a handle made by this engine's make_loss / make_index_lists (and not freed)")
         rtol = 1e-7 if rtol is None else rtol
@@ -451,7 +470,7 @@ class NetworkEngine:
 
     @staticmethod
     def _opts(method: str, kernel: str, **kw):
-        return _capi.default_opts(linsolve=("structured" if kernel == "lds" else "auto"), kernel=("workspace" if kernel == "workspace" else "auto"),
+        return _capi.default_opts(linsolve=("structured" if kernel == "lds" else "auto"), kernel=(kernel if kernel in ("workspace", "hbm") else "auto"),
                                   method={"dp5": "dp5", "ark": "ark436", "rosw": "ros34pw2"}.get(method), **kw)
 
     def workspace_bytes(self, B: int) -> int:

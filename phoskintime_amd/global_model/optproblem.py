@@ -72,7 +72,8 @@ class GlobalODEBatch:
         and their exact discrete derivative with respect to the RAW entries ``cols`` from one launch
         (``NetworkEngine.simulate_objective_grad_batch`` with the problem's tolerances, loss mode, defaults and lambdas).  F comes from
         the order-3 integrator with the tangents in its error norm, so it is within the tolerances of ``evaluate_device``'s, not
-        bit-equal to it.  Raises PhoskinError where the launch is refused (``pk_last_error`` names the remedy)."""
+        bit-equal to it.  Networks of any size: where not one tangent column fits in a workgroup's LDS the launch runs on HBM slabs by
+        itself.  Raises PhoskinError where the launch is refused (``pk_last_error`` names the remedy)."""
         out = self.eng.simulate_objective_grad_batch(
             self.loss, X, self.time_grid, cols, y0=self.y0, raw=True, rtol=self.rtol, atol=self.atol, max_steps=self.max_steps * self.time_grid.size,
             err_norm=self.err_norm, loss_mode=self.loss_mode, defaults=self.defaults, lambdas=self.lam, fail_value=self.fail_value,

@@ -246,8 +246,9 @@ def local_sensitivity_batch(eng: NetworkEngine, params: Dict, t_prot, t_rna, t_p
     differencing ``simulate_batch`` takes two solves per entry and loses accuracy at the tolerances in use.  The network twin of
     ``sensitivity.analysis.local_sensitivity_batch``.  ``vary``: names (``"c_k_0"``, ``"A_i_1"``, ``"tf_scale"``, as ``compute_bounds``
     names them) or indices into the flat parameter vector; None = every entry -- but this is a tool for a chosen handful of entries: a
-    launch costs about (1 + KC) / KC state integrations per column (KC = ``eng.sens_columns_per_launch()``), a full gradient needs an
-    adjoint.  Returns a dict with
+    launch costs about (1 + KC) / KC state integrations per column (KC = ``eng.sens_columns_per_launch()``; on networks beyond one
+    workgroup's LDS the launch runs on HBM slabs by itself, KC = ``eng.sens_hbm_columns(K)``), a full gradient needs an adjoint.
+    Returns a dict with
 
       names       the K varied entries
       layout      the index lists (``make_index_lists``) pred's rows follow, times the union grid
