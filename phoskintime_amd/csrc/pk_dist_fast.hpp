@@ -645,7 +645,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       const bool over = (CFG::LITERAL ? nacc + nsec : nsec) >= A.max_steps;
       const bool last = (tc + 1.0001 * h >= te);
       const double hs = last ? te - tc : ((tc + 2.0 * h > te) ? 0.5 * (te - tc) : h);
-      if (over || !(hs > 1e-14 * fmax(fabs(tc), 1e-3))) { status |= over ? PK_ST_MAXSTEPS : PK_ST_HMIN; break; }
+      // max_abs_k, and max_raw / min_raw in the controller below: one v_max_f64 / v_min_f64 each (pk_wave.hpp), same bits as fmax / fmin
+      if (over || !(hs > 1e-14 * max_abs_k(tc, 1e-3))) { status |= over ? PK_ST_MAXSTEPS : PK_ST_HMIN; break; }
       if constexpr (PARK) {
         // the site rows of the state live in their slots between steps: read here (next to the rate slots, whose wait they share),
         // written by the lanes that accept -- a rejecting lane has nothing to undo and an accepting one nothing to copy
@@ -718,16 +719,19 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         ++nsec;
         if (__builtin_expect(err != err || err > 1e300, 0)) { after_reject = true; h = 0.1 * hs; nonfin = true; break; }
       }
-      double fac = root_q(err, Tab::Q) * (1.0 / 0.9);
-      fac = fmax(1.0 / 6.0, fmin(5.0, fac));
-      double hnew = hs * fast_rcp(fac);
+      // The controller as a multiplier: err^(-1/Q) by negating the exponent of root_q (pk_solve_kernel.hpp; its two clamps inlined as
+      // single instructions), then step_growth's clamps [1/5, 6] -- hs / step_fac(err^(1/Q)) without the reciprocal of a factor that
+      // v_log_f32 / v_exp_f32 leave good to 1e-7 anyway.  h moves by an ulp or two of single precision against the quotient
+      const float e32 = (float)min_raw_k(max_raw_k(err, 1e-30), 1e30);
+      const double finv = step_growth((double)__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(e32) * (float)(-1.0 / Tab::Q)));
+      double hnew = hs * finv;
       const bool land = acc && last;
       if constexpr (CFG::LITERAL) { nacc += acc ? 1 : 0; nsec += acc ? 0 : 1; }
       else nacc += (int)acc;                            // the predicate itself: 0 or 1
-      if (acc && after_reject) hnew = fmin(hnew, hs);
+      if (acc && after_reject) hnew = min_raw(hnew, hs);
       after_reject = !acc;
       if constexpr (CFG::LITERAL) tc = land ? te : (acc ? tc + hs : tc);
-      h = (land && hs < h) ? fmax(hnew, h) : hnew;
+      h = (land && hs < h) ? max_raw(hnew, h) : hnew;
       if (land) {
         // a landing sets the time to the output time itself (tc + hs is te only up to rounding); the accept above has already moved
         // tc, which nothing reads in between

@@ -61,7 +61,8 @@ struct DistNorm {
   const double rtol, atol;
   const int lane;
   __device__ __forceinline__ double ratio(double e, double ya, double yb) const {
-    return fabs(e) * approx_rcp(__builtin_fma(rtol, fmax(fabs(ya), fabs(yb)), atol));
+    // max_abs: fmax(fabs(ya), fabs(yb)) in one v_max_f64 |ya|, |yb| (same bits, a NaN operand dropped as fmax drops it)
+    return fabs(e) * approx_rcp(__builtin_fma(rtol, max_abs(ya, yb), atol));
   }
   // NaN-propagating: the initial step estimate; DistAny
   __device__ __forceinline__ double group_max(const Vec& num, const Vec& a, const Vec& b) const {

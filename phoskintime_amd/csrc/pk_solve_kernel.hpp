@@ -106,7 +106,9 @@ template <> struct ResolventTab<PK_METHOD_LRP12> {
                                     0.73000709527912039739};
 };
 
-// err^(1/Q) for the step-size controller: single precision is ample (the factor is clamped to [1/6, 5] anyway)
+// err^(1/Q) for the step-size controller: single precision is ample (the factor is clamped to [1/6, 5] anyway).  dist_fast_kernel does not
+// call it: it states the same three operations itself with the exponent negated (err^(-1/Q) for step_growth, pk_step.hpp) and the two
+// clamps of err as single instructions (pk_wave.hpp: max_raw_k / min_raw_k).  Every other integrator divides by step_fac(root_q(err, Q)).
 __device__ __forceinline__ double root_q(double err, double Q) {
   const float e = (float)fmin(fmax(err, 1e-30), 1e30);
   return (double)__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(e) * (float)(1.0 / Q));

@@ -182,6 +182,21 @@ __device__ __forceinline__ double gmax(double v, int lane) {
   return v;
 }
 
+// ---- maxima and minima as exactly ONE v_max_f64 / v_min_f64.  In front of fmax / fmin the compiler quiets a possible signalling NaN
+// with a canonicalising v_max_f64 x, x, x on every operand it cannot prove canonical -- fabs() of a value read back from LDS, the result
+// of a DPP move, the result of a select.  In IEEE mode (every kernel here runs in it) the instruction quiets a signalling NaN itself and
+// returns the other operand for a NaN: the bits fmax / fmin give, without the extra instruction.  Plain (non-volatile) asm that holds
+// nothing but the instruction: the compiler schedules it, drops it when unused, and still places the wait states a DPP read of its
+// result needs.  max_abs takes |.| of both sources in the same instruction (the source modifiers of VOP3).
+// The _k forms take a compile-time constant as their second operand, in an SGPR pair ("s"): no VGPR pair is spent on it.  The constant
+// must be uniform over the wave -- pass a literal, nothing else.
+__device__ __forceinline__ double max_raw(double a, double b) { double d; asm("v_max_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+__device__ __forceinline__ double min_raw(double a, double b) { double d; asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+__device__ __forceinline__ double max_abs(double a, double b) { double d; asm("v_max_f64 %0, |%1|, |%2|" : "=v"(d) : "v"(a), "v"(b)); return d; }
+__device__ __forceinline__ double max_raw_k(double a, double k) { double d; asm("v_max_f64 %0, %1, %2" : "=v"(d) : "v"(a), "s"(k)); return d; }
+__device__ __forceinline__ double min_raw_k(double a, double k) { double d; asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "s"(k)); return d; }
+__device__ __forceinline__ double max_abs_k(double a, double k) { double d; asm("v_max_f64 %0, |%1|, %2" : "=v"(d) : "v"(a), "s"(k)); return d; }
+
 // ---- the plain maximum (one v_max_f64 per pair and per level): a NaN operand is DROPPED, +inf wins.  For callers that surface a NaN
 // themselves (the step loop of pk_dist_fast.hpp turns it into +inf before the reduction); finite values give the bits gmax gives.
 template <int LO, int HI, int N>
@@ -203,12 +218,13 @@ __device__ __forceinline__ bool any_nan(const double (&v)[N]) {
 }
 template <int G>
 __device__ __forceinline__ double gmax_num(double v, int lane) {
-  if constexpr (G >= 2)  v = __builtin_fmax(v, partner<1>(v, lane));
-  if constexpr (G >= 4)  v = __builtin_fmax(v, partner<2>(v, lane));
-  if constexpr (G >= 8)  v = __builtin_fmax(v, partner<4>(v, lane));
-  if constexpr (G >= 16) v = __builtin_fmax(v, partner<8>(v, lane));
-  if constexpr (G >= 32) v = __builtin_fmax(v, partner<16>(v, lane));
-  if constexpr (G >= 64) v = __builtin_fmax(v, partner<32>(v, lane));
+  // max_raw: the result of a DPP move is not canonical to the compiler, and fmax would quiet it first (one more v_max_f64 per level)
+  if constexpr (G >= 2)  v = max_raw(v, partner<1>(v, lane));
+  if constexpr (G >= 4)  v = max_raw(v, partner<2>(v, lane));
+  if constexpr (G >= 8)  v = max_raw(v, partner<4>(v, lane));
+  if constexpr (G >= 16) v = max_raw(v, partner<8>(v, lane));
+  if constexpr (G >= 32) v = max_raw(v, partner<16>(v, lane));
+  if constexpr (G >= 64) v = max_raw(v, partner<32>(v, lane));
   return v;
 }
 

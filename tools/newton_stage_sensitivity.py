@@ -177,8 +177,9 @@ class Lanes:
         return yn, (abs(LE[1]) / GAM) * z
 
 
-def lrp12_newton(th, n, G, RPL, y0, t, tabs, resident, rtol=RTOL, atol=ATOL, max_steps=100000, h0=0.0):
-    """One replica, whole integration, the step loop's controller around Lanes.step.  (sol [T, n + 2], status, accepted, rejected)"""
+def lrp12_newton(th, n, G, RPL, y0, t, tabs, resident, rtol=RTOL, atol=ATOL, max_steps=100000, h0=0.0, controller=None):
+    """One replica, whole integration, the step loop's controller around Lanes.step.  (sol [T, n + 2], status, accepted, rejected)
+    controller(hs, err, Q) -> hnew replaces the double-precision rule (tools/controller_growth_sensitivity.py)"""
     GAM, NS = tabs[0], len(tabs[1])
     L = Lanes(th, n, G, RPL, resident)
     y = L.load(y0)
@@ -215,9 +216,12 @@ def lrp12_newton(th, n, G, RPL, y0, t, tabs, resident, rtol=RTOL, atol=ATOL, max
                 if not (np.isfinite(y).all() and np.isfinite(th[:4 + 2 * n]).all()):
                     status |= 1; break
                 continue
-            fac = min(max(err, 1e-30), 1e30) ** (1.0 / (NS - 1.0)) / 0.9
-            fac = max(1.0 / 6.0, min(5.0, fac))
-            hnew = hs / fac
+            if controller is not None:
+                hnew = controller(hs, err, NS - 1.0)
+            else:
+                fac = min(max(err, 1e-30), 1e30) ** (1.0 / (NS - 1.0)) / 0.9
+                fac = max(1.0 / 6.0, min(5.0, fac))
+                hnew = hs / fac
             if err <= 1.0:
                 acc += 1
                 y = yn; tc += hs
