@@ -304,6 +304,22 @@ int pk_morris_build_batch(pk_ctx*, int64_t N, int D, double delta, const double*
 /* Elementary effects EE [N,D] from the per-row outputs Y [N (D+1)] of the same design: (Y[r, rank+1] - Y[r, rank]) / (sign * delta). */
 int pk_morris_effects_batch(pk_ctx*, int64_t N, int D, double delta, const double* sign, const int32_t* rank, const double* Y, double* EE);
 
+/* Variance-based (Sobol') indices without a host round trip (reference: SALib saltelli.sample / sobol.analyze with
+ * calc_second_order=False as called at scripts/temporal_sensitivity.py:169,185).  The two N x D base samples A, B on the unit cube come
+ * from the host (KB); the N (D + 2) x D design is built in HBM in saltelli.sample's row order: for each i the row A_i, then
+ * AB_i1 .. AB_iD (A_i with column j taken from B_i), then B_i, each scaled as lb + u (ub - lb) with separately rounded multiply and add.
+ * All pointers are device pointers. */
+int pk_sobol_build_batch(pk_ctx*, int64_t N, int D, const double* A, const double* B, const double* lb, const double* ub, double* X);
+/* First-order and total indices S1, ST [D,M] of the M output columns Y [N (D + 2), M] (row-major, rows in the design's order), each column
+ * centred by its mean over all rows:  S1_j = mean(B (AB_j - A)) / var([A; B]),  ST_j = mean((A - AB_j)^2) / 2 / var([A; B])  with the
+ * population variance, also written to var [M] (optional).  counts [R,N] (int32): row r holds how often resample r draws each i; its
+ * indices are the same formulas with weights counts[r,i] / N (its own variance included), and S1_sd, ST_sd [D,M] are their ddof-1
+ * standard deviations over the R resamples (no normal quantile).  R = 0: no resampling, counts / S1_sd / ST_sd ignored; R = 1 is an error.
+ * A column whose maximum equals its minimum is NaN in every output.  Every sum is one thread's sequential sum over i: an entry (j, m)
+ * is bit-equal whatever D, M and R surround it.  M = 0 is PK_OK. */
+int pk_sobol_indices_batch(pk_ctx*, int64_t N, int D, int64_t M, const double* Y, const int32_t* counts, int R,
+                           double* S1, double* ST, double* S1_sd, double* ST_sd, double* var);
+
 /* Replaces config.config.score_fit(params, target, prediction, alpha, beta, gamma, delta, mu) (config/config.py:176-226) for B
  * candidates: theta [B,P], target [N] (shared), pred [B,N] (e.g. the `flat` output) -> out [B].  weights = {alpha (rmse), beta (mae),
  * gamma (var), delta (mse), mu (l2)} as a HOST pointer, NULL = all 1 (config/constants.py:77-83). */

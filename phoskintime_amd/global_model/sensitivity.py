@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from ..sensitivity import morris
+from ..sensitivity import sobol
 from ..distributed import interleaved_rows, all_gather_interleaved_with_status, shared_seed
 from . import config
 from .engine import NetworkEngine
@@ -184,6 +185,89 @@ def run_sensitivity_batch(eng: NetworkEngine, fitted_params: Dict, times_p, time
     if return_pred:
         out.update(pred=pred, layout=ld, rows=rows.cpu().numpy(), times=times)
     return out
+
+
+def temporal_gsa_batch(eng: NetworkEngine, params: Dict, time_grid=(0, 5, 15, 30, 60, 90, 120), vary=None, perturbation: float = 0.5,
+                       n_samples: int = 128, seed: Optional[int] = None, num_resamples: int = 100, conf_level: float = 0.95, proteins=None,
+                       y0=None, rtol: Optional[float] = None, atol: Optional[float] = None, fused: bool = False, method: str = "auto",
+                       kernel: str = "auto", return_pred: bool = False) -> Dict:
+    """Time-resolved Sobol' indices of EVERY protein's fold-change trajectory from ONE Saltelli batch: the numerical core of
+    ``run_full_gsa`` (scripts/temporal_sensitivity.py:143-188) for all proteins at once.  The reference draws the same design once per
+    protein, runs its n_samples (D + 2) LSODA solves, keeps one protein's trajectory of each and analyses it once per time point; here the
+    design is built in HBM (``sobol.sample_device``), scattered into copies of the packed vector, integrated in one launch, and the
+    [n_samples (D + 2), N_prot T] fold changes are reduced to indices, bootstrap included, on the device (``sobol.indices_device``).
+
+    ``params`` maps the eight parameter groups (``run_sensitivity_batch``'s ``fitted_params``).  ``vary=None`` is the reference's problem:
+    every ``c_k`` plus ``E_i`` of every protein that acts as a TF -- read from the column indices of the engine's TF matrix, the one
+    deviation: the engine keeps the matrix, not the edge table the reference looks the names up in.  ``vary`` also takes names
+    (``"c_k_0"``, ``"E_i_3"``) or indices into the flat parameter vector.  Bounds are [v (1 - perturbation), v (1 + perturbation)] with no
+    special case for zero values.  ``fused=True`` forms the fold changes inside the order-3 integrator (``simulate_measure_batch``;
+    ``method`` / ``kernel`` defaults as ``run_sensitivity_batch(fused=True)``); a refused launch raises ``PhoskinError`` with the
+    library's reason.  Tolerances default to ``measure_tolerances``, ``max_steps`` is 5000 T.  Rows with ``status != 0`` and non-finite
+    entries become 0, as the reference's worker returns zeros.  ``seed=None`` draws one; the bootstrap uses
+    ``sobol.resample_counts(n_samples, num_resamples, seed)`` (``num_resamples`` 0 or >= 2).  Single process: the rows are not sharded.
+
+    Returns a dict: ``ST``, ``S1``, ``ST_conf``, ``S1_conf`` [T, N_prot, D] (only the rows ``proteins`` when given); ``heatmap`` =
+    max(ST, 0) with NaN -> 0 (the reference's ``max(0, st_val)``; ST is NaN where a column is constant, as at the baseline time);
+    ``names``, ``problem``, ``times``, ``param_values`` [n_samples (D + 2), D], ``status``, ``mean_steps``, ``seed``; with
+    ``return_pred``: ``pred`` [rows, N_prot T] (GPU tensor, column p T + k, after the zeroing) and ``layout``."""
+    p = {k: (np.asarray(params[k], float) if k != "tf_scale" else float(params[k])) for k in _ORDER}
+    from .simulate import measure_tolerances
+    tol = measure_tolerances(eng)
+    rtol = tol["rtol"] if rtol is None else rtol
+    atol = tol["atol"] if atol is None else atol
+    names_all = compute_bounds(p, perturbation)["names"]
+    center = eng.pack_params(*(p[k] for k in _ORDER))
+    if vary is None:
+        e0 = eng.n_K + 4 * eng.N + eng.total_sites                         # [c_k | A_i | B_i | C_i | D_i | Dp_i | E_i | tf_scale]
+        vidx = np.concatenate([np.arange(eng.n_K), e0 + np.unique(eng._keep[7]).astype(np.int64)]).astype(np.int64)
+    else:
+        pos = {nm: i for i, nm in enumerate(names_all)}
+        vidx = np.array([pos[v] if isinstance(v, str) else int(v) for v in vary], dtype=np.int64)
+    if vidx.size == 0 or np.unique(vidx).size != vidx.size or vidx.min() < 0 or vidx.max() >= len(names_all):
+        raise ValueError("vary must hold distinct indices (or names) of the flat parameter vector")
+    v = center[vidx]
+    problem = {"num_vars": int(vidx.size), "names": [names_all[i] for i in vidx],
+               "bounds": [[float(x * (1 - perturbation)), float(x * (1 + perturbation))] for x in v]}
+    times = np.asarray(time_grid, dtype=np.float64)
+    if times.ndim != 1 or times.size < 1 or np.any(np.diff(times) <= 0):
+        raise ValueError("time_grid must be strictly increasing")
+    T, D = times.size, int(vidx.size)
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1)[0])
+    counts = sobol.resample_counts(n_samples, num_resamples, seed) if num_resamples else None
+    Xv, design = sobol.sample_device(problem, N=n_samples, seed=seed, device=eng.ctx.device)
+    Xd = torch.as_tensor(center, device=Xv.device).repeat(Xv.shape[0], 1)  # scatter the varied columns into copies of the packed vector (in HBM)
+    Xd[:, torch.as_tensor(vidx, device=Xv.device)] = Xv
+    lists, ld = eng.make_index_lists(times, times, [], [])                  # protein fold changes only: column p T + k
+    n_obs = ld["p_prot"].size
+    try:
+        if fused:
+            out = eng.simulate_measure_batch(lists, Xd, times, y0=y0, rtol=rtol, atol=atol, max_steps=5000 * T, eps=1e-12, want_pred=True,
+                                             method=("rosw" if method == "auto" else method), kernel=("lds" if kernel == "auto" else kernel))
+            if out is None:
+                from .. import _capi
+                raise _capi.PhoskinError("temporal_gsa_batch(fused=True): the fused launch was refused: "
+                                         + (eng.ctx.lib.pk_last_error(eng.ctx.handle) or b"").decode() + " -- or call with fused=False")
+            _, pred, status, nst, _ = out
+        else:
+            Y, status, nst = eng.simulate_batch(Xd, times, y0=y0, rtol=rtol, atol=atol, max_steps=5000 * T, method=method, kernel=kernel)
+            pred = eng.observables_batch(lists, Y, n_obs, eps=1e-12)
+        pred = torch.where((status != 0)[:, None], torch.zeros_like(pred), pred)      # a failed simulation contributes a zero trajectory
+        pred = torch.nan_to_num(pred, nan=0.0, posinf=0.0, neginf=0.0)
+        idx = sobol.indices_device(design, pred, counts, conf_level)
+        torch.cuda.current_stream().synchronize()
+    finally:
+        eng.free_loss(lists)
+    sel = np.arange(eng.N) if proteins is None else np.asarray(proteins, dtype=np.int64)
+    shape = lambda a: np.ascontiguousarray(a.cpu().numpy().reshape(D, eng.N, T).transpose(2, 1, 0)[:, sel, :])      # [D, p T + k] -> [T, N_prot, D]
+    res = {k: shape(idx[k]) for k in ("ST", "S1", "ST_conf", "S1_conf")}
+    res["heatmap"] = np.where(np.isnan(res["ST"]), 0.0, np.maximum(res["ST"], 0.0))
+    res.update(names=problem["names"], problem=problem, times=times, param_values=Xv.cpu().numpy(), status=status.cpu().numpy(),
+               mean_steps=[float(x) for x in nst.double().mean(dim=0).cpu()], seed=seed)
+    if return_pred:
+        res.update(pred=pred, layout=ld)
+    return res
 
 
 _METRICS = ("total_signal", "mean", "variance", "l2_norm")

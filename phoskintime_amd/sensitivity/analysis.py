@@ -10,6 +10,8 @@
                                        with _compute_Y formed in the kernels' output stage), with elasticities and box-scaled slopes
   sensitivity_analysis_batch           the numerical core of _sensitivity_analysis: sample -> N*(D+1) solves + Y in
                                        ONE launch -> analyze -> RMSE ranking against data -> best K curves (no plotting)
+  temporal_sobol_batch                 not in the reference's per-protein path: Sobol' indices of every entry of ``flat`` from one Saltelli
+                                       batch (the per-protein twin of global_model.sensitivity.temporal_gsa_batch)
 """
 from __future__ import annotations
 
@@ -165,6 +167,38 @@ def local_sensitivity_batch(theta, time_points, num_psites: int, init_cond, mode
     zero = (Y == 0.0)[:, None]
     elasticity = np.where(zero, 0.0, th * dY / np.where(zero, 1.0, Y[:, None]))
     return {"names": names, "Y": Y, "dY": dY, "elasticity": elasticity, "scaled": dY * width, "status": res.status.cpu().numpy()}
+
+
+def temporal_sobol_batch(model, popt: Sequence[float], y0, num_psites: int, t, perturbation: Optional[float] = None, n_samples: int = 128,
+                         seed: Optional[int] = None, num_resamples: int = 100, conf_level: float = 0.95, return_flat: bool = False,
+                         **solver_kw) -> Dict:
+    """Sobol' indices of every entry of ``flat`` (each observable at each time) around a fitted parameter vector: the per-protein twin of
+    ``global_model.sensitivity.temporal_gsa_batch``, on the same two kernels.  A Saltelli design of n_samples (P + 2) rows within
+    ``compute_bound(v, perturbation)`` of every parameter is built in HBM, integrated by ONE ``solve_ode_batch`` launch, and its output
+    matrix ``flat`` [rows, F] is reduced to indices on the device (``sobol.indices_device``); flagged rows and non-finite entries count
+    as 0.  The bootstrap uses ``sobol.resample_counts(n_samples, num_resamples, seed)`` (``num_resamples`` 0 or >= 2; ``seed=None`` draws
+    one).  Returns a dict: ``S1``, ``ST``, ``S1_conf``, ``ST_conf`` [F, P] in ``flat``'s order (NaN where an entry does not vary over
+    the design), ``names``, ``problem``, ``param_values``, ``status``, ``seed``; with ``return_flat``: ``flat`` (GPU tensor)."""
+    import torch
+    from .. import batch
+    from . import sobol
+    popt = np.asarray(popt, dtype=float)
+    define = define_sensitivity_problem_rand if batch.model_id(model) == batch.RAND else define_sensitivity_problem_ds
+    problem = define(num_psites, list(popt))
+    problem["bounds"] = [compute_bound(v, perturbation) for v in popt]
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1)[0])
+    counts = sobol.resample_counts(n_samples, num_resamples, seed) if num_resamples else None
+    Xd, h = sobol.sample_device(problem, N=n_samples, seed=seed, device=solver_kw.get("device"))
+    res = batch.solve_ode_batch(model, Xd, y0, num_psites, t, want_sol=False, want_flat=True, **solver_kw)
+    flat = torch.where((res.status != 0)[:, None], torch.zeros_like(res.flat), res.flat)
+    flat = torch.nan_to_num(flat, nan=0.0, posinf=0.0, neginf=0.0)
+    idx = sobol.indices_device(h, flat, counts, conf_level)
+    out = {k: idx[k].cpu().numpy().T.copy() for k in ("S1", "ST", "S1_conf", "ST_conf")}
+    out.update(names=problem["names"], problem=problem, param_values=Xd.cpu().numpy(), status=res.status.cpu().numpy(), seed=seed)
+    if return_flat:
+        out["flat"] = flat
+    return out
 
 
 def _perturb_solve(i_X_tuple):
