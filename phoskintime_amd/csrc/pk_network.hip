@@ -11,6 +11,7 @@
 #include "pk_network_solve_reg2.hpp"
 #include "pk_network_rk45.hpp"
 #include "pk_network_sens.hpp"
+#include "pk_net_plan.hpp"
 namespace pk {
 // persistent grid: min(B, workgroups of `kernel` at `threads` each resident on the current device at once)
 hipError_t net_persistent_grid(const void* kernel, int threads, long long B, int* grid);
@@ -312,206 +313,164 @@ int pk_network_jacobian_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, 
   return e == hipSuccess ? PK_OK : pk_ctx_fail(c, PK_ERR_HIP, hipGetErrorString(e));
 }
 
-// Which kernel pk_network_simulate_batch runs for these options on this network, and with which method: the single source of truth (the
-// Python host layer picks its default tolerances from the method).  PK_METHOD_DP5 on request; PK_METHOD_ARK436 where its kernel fits and
-// is the default (or was asked for); otherwise PK_METHOD_ROS34PW2.  ROS34PW2 always runs on the workspace kernel for networks beyond the
-// one-workgroup LDS kernels (S > 1024, N > 512, or more than 160 KiB of LDS for the general one; small combinatorial blocks run out of
-// registers and are exempt) and on request (opts->kernel = PK_KERNEL_WORKSPACE).  A refused plan has code PK_ERR_UNSUPPORTED and a
-// message; its method is then PK_ERR_UNSUPPORTED, except for a DP5 request on a network too large for the DP5 kernel.  PK_KERNEL_HBM is
-// read by the two sensitivity entry points alone (they translate it before they plan): every other caller of this plan is refused.
-enum class NetKernel { DP5, Workspace, ArkPair, Ark, CombReg, Reg, Lds };
-struct NetPlan {
-  int method;
-  NetKernel kernel;
-  int code;
-  const char* refusal;
-  int threads;                                   // ARK and register kernels: one thread per protein, in whole waves
-};
+// Which kernel a network launch runs, with which method, or why not: net_plan of pk_net_plan.hpp, the single source of truth for every
+// flavour (the Python host layer picks its default tolerances from the method).  Here: what the plan is told about this network
+// (net_facts) and about the environment (net_switches), both read at every call.
+using pk::NetFlavour; using pk::NetKernel; using pk::NetPlan;
 
-static NetPlan net_plan(const pk_net* n, const pk_solver_opts* opts) {
-  const pk::NetDev& d = n->d;
-  const int method = opts ? opts->method : PK_METHOD_LRP12;
-  const bool structured = opts && opts->linsolve == PK_LINSOLVE_STRUCTURED;
-  const bool ws_forced = opts && opts->kernel == PK_KERNEL_WORKSPACE;
-  const int threads = ((d.N + 63) / 64) * 64;
-  auto take = [&](int m, NetKernel k) { return NetPlan{m, k, PK_OK, nullptr, threads}; };
-  auto refuse = [&](int m, const char* why) { return NetPlan{m, NetKernel::Lds, PK_ERR_UNSUPPORTED, why, threads}; };
-  if (opts && opts->kernel == PK_KERNEL_HBM)
-    return refuse(PK_ERR_UNSUPPORTED, "PK_KERNEL_HBM is read by pk_network_simulate_sens_batch and pk_network_simulate_objective_grad_batch only; "
-                                      "ask for PK_KERNEL_WORKSPACE here");
-  if (method == PK_METHOD_DP5) {
-    if (ws_forced) return refuse(PK_ERR_UNSUPPORTED, "PK_KERNEL_WORKSPACE integrates with PK_METHOD_ROS34PW2 only");
-    if (d.S > 1024 || d.N > 512) return refuse(PK_METHOD_DP5, "PK_METHOD_DP5: S <= 1024 states and N <= 512 proteins per network");
-    if (pk::net_rk45_lds_bytes(d) > 160 * 1024) return refuse(PK_METHOD_DP5, "network too large for one workgroup's LDS (160 KiB)");
-    return take(PK_METHOD_DP5, NetKernel::DP5);
-  }
-  // combinatorial blocks: <= 3 sites per protein (and N <= 256) run one thread per protein out of registers (pk_network_solve_reg2.hpp);
-  // larger blocks run in the general LDS kernel with the same approximate factorisation, swept serially by the protein's thread
-  const bool comb_reg = d.model == 2 && n->max_sites <= 3 && d.N <= 256;
-  if (ws_forced || d.S > 1024 || d.N > 512 || (!comb_reg && n->solve_lds_bytes > 160 * 1024)) {
-    if (method == PK_METHOD_ARK436)
-      return refuse(PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: not on the workspace kernel (networks beyond one workgroup's LDS); use PK_METHOD_ROS34PW2");
-    return take(PK_METHOD_ROS34PW2, NetKernel::Workspace);
-  }
-  // one thread per protein (N <= 256), or [r3] the dense lane layout of topologies 0 / 1 / 4 (<= 512 lanes: up to 512 proteins)
-  const bool ark_fits = d.N <= 256 && n->max_sites <= (d.model == 2 ? 3 : 8) && !structured;
-  const bool pair = pk::net_arkp_fits(d, n->max_sites);
-  const bool ark_ok = (ark_fits && pk::net_ark_lds_bytes(d, n->nnzT, n->max_sites, threads) <= 160 * 1024) || (!structured && pair);
-  if (method == PK_METHOD_ARK436 && !ark_ok)
-    return refuse(PK_ERR_UNSUPPORTED, "PK_METHOD_ARK436: <= 8 sites per protein and N <= 256 (topologies 0 / 1 / 4: <= 512 lanes of the dense layout); "
-                                      "combinatorial topology: <= 3 sites, N <= 256; use PK_METHOD_ROS34PW2");
-  // [r3] the combinatorial topology takes the additive method by default too: with the EXACT block solve (parity elimination of the
-  // bit-pattern block, pk_network_solve_ark.hpp) it needs 4.6x fewer steps than the order-3 method and runs 1.8x faster at equal band error
-  if (ark_ok && method != PK_METHOD_ROS34PW2) return take(PK_METHOD_ARK436, pair ? NetKernel::ArkPair : NetKernel::Ark);
-  // ROS34PW2: the register-resident kernels (one thread per protein) when every block fits their per-thread arrays; opts->linsolve ==
-  // PK_LINSOLVE_STRUCTURED forces the LDS kernel (kept as the general fallback and as the A/B reference)
-  if (comb_reg && !structured) return take(PK_METHOD_ROS34PW2, NetKernel::CombReg);
-  if (d.model != 2 && d.N <= 256 && n->max_sites <= 8 && n->solve_reg_lds_bytes <= 64 * 1024 && !structured)
-    return take(PK_METHOD_ROS34PW2, NetKernel::Reg);
-  return take(PK_METHOD_ROS34PW2, NetKernel::Lds);
+// dev knob PK_NET_SENS_KC: a column count below `cap`
+static int net_sens_kc(int cap) {
+  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < cap) return v; }
+  return cap;
 }
 
-int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) { return n ? net_plan(n, opts).method : PK_ERR_ARG; }
+// Columns one workgroup of the sensitivity kernel carries on this network: the largest count whose LDS request (net_sens_lds_bytes; `score`:
+// net_sens_score_lds_bytes -- the rna baseline, its tangents and the accumulators come on top) stays within 160 KiB, at most n_var; 0 where
+// not even one fits or the network is beyond the LDS kernel's thread layout.  Host arithmetic only (dev knob PK_NET_SENS_KC: a smaller count)
+static int net_sens_lds_columns(const pk_net* n, bool score) {
+  if (n->d.S > 1024 || n->d.N > 512) return 0;
+  const int fit = score ? pk::net_sens_score_max_columns(n->d, n->nnzT, pk::kNetLdsLimit) : pk::net_sens_max_columns(n->d, n->nnzT, pk::kNetLdsLimit);
+  return net_sens_kc(std::min(fit, n->d.n_var));
+}
 
-// `fused`: null, or the loss fields of NetSolveArgs filled in (pk_network_simulate_objective_batch); Y may then be null.  With
-// fused->loss_ptr set (the time-bucketed lists: the caller asked for the order-3 method or the workspace kernel) the launch runs where the
-// plan's kernel is Lds or Workspace; with the dense tables, on the dense-lane additive kernel.  fused->meas: the same lists measured
-// instead of scored (pk_network_simulate_measure_batch), on the same two kernels.  `sens`: null, or the columns of
-// pk_network_simulate_sens_batch (cols: HOST pointer; Y may then be null): the plan must be the general LDS kernel, or with sens->hbm the
-// workspace kernel (the tangents on slabs).  sens->score: the scoring flavour (pk_network_simulate_objective_grad_batch); `fused` then
-// carries the loss lists, the permutation and the loss outputs
-struct NetSensReq { const int32_t* cols_host; int K, KC; double* dY; const pk::NetSensScoreArgs* score = nullptr; bool hbm = false; };
+static pk::NetFacts net_facts(const pk_net* n) {
+  const pk::NetDev& d = n->d;
+  return {d.model, d.N, d.S, d.n_var, n->max_sites,
+          n->solve_lds_bytes, pk::net_solve_fused_lds_bytes(d, n->nnzT), n->solve_reg_lds_bytes, pk::net_rk45_lds_bytes(d),
+          pk::net_ark_lds_bytes(d, n->nnzT, n->max_sites, ((d.N + 63) / 64) * 64),
+          pk::net_arkp_fits(d, n->max_sites), pk::net_arkp_fuses_loss(), net_sens_lds_columns(n, false), net_sens_lds_columns(n, true)};
+}
+
+static pk::NetSwitches net_switches() {
+  const char* e = getenv("PK_NET_THREADS");
+  return {e ? atoi(e) : 0, net_sens_kc(16)};
+}
+
+static pk_solver_opts net_opts(const pk_solver_opts* opts) {
+  pk_solver_opts o;
+  if (opts) o = *opts; else pk_default_opts(&o);
+  return o;
+}
+
+int pk_network_resolve_method(const pk_net* n, const pk_solver_opts* opts) {
+  return n ? pk::net_plan(net_facts(n), net_opts(opts), NetFlavour::Plain, 0, net_switches()).method : PK_ERR_ARG;
+}
+
+// The columns of a tangent launch (cols: HOST pointer, K >= 1) with the plan their entry point made for them -- it answers the plan's
+// refusals before it checks cols.  score: the scoring flavour's outputs (pk_network_simulate_objective_grad_batch)
+struct NetSensReq { const int32_t* cols_host; int K; double* dY; const pk::NetSensScoreArgs* score; NetPlan plan; };
+
+// Landing points of a launch: every output time after t[0] plus every bucket edge strictly inside (t[0], t[T-1]); the explicit integrator
+// interpolates its outputs and needs the T output times only.  Up to 64 travel in the kernel arguments, more through a per-network buffer
+static int net_landing_points(pk_ctx* c, pk_net* n, const double* t_host, int T, bool dp5, pk::NetSolveArgs& a) {
+  std::vector<std::pair<double, int>> st;
+  for (int k = dp5 ? 0 : 1; k < T; ++k) st.push_back({t_host[k], k});
+  if (!dp5) {
+    for (double gk : n->kin_grid_host) {
+      if (gk > t_host[0] && gk < t_host[T - 1]) {
+        bool dup = false;
+        for (int k = 1; k < T; ++k) if (t_host[k] == gk) { dup = true; break; }
+        if (!dup) st.push_back({gk, -1});
+      }
+    }
+    std::sort(st.begin(), st.end());
+  }
+  a.n_stops = (int)st.size();
+  if (st.size() <= 64) {
+    for (size_t i = 0; i < st.size(); ++i) { a.stops_v[i] = st[i].first; a.stop_out_v[i] = st[i].second; }
+    return PK_OK;
+  }
+  // long output grids: stage through a per-network device buffer (the previous launch on it must have finished)
+  std::lock_guard<std::mutex> g(n->mu);
+  if (hipDeviceSynchronize() != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipDeviceSynchronize");      // any stream of any context
+  if (n->stops_cap < st.size()) {
+    if (n->stops_dev) (void)hipFree(n->stops_dev);
+    if (n->stop_out_dev) (void)hipFree(n->stop_out_dev);
+    n->stops_dev = nullptr; n->stop_out_dev = nullptr; n->stops_cap = 0;
+    if (hipMalloc((void**)&n->stops_dev, st.size() * 8) != hipSuccess || hipMalloc((void**)&n->stop_out_dev, st.size() * 4) != hipSuccess)
+      return pk_ctx_fail(c, PK_ERR_NOMEM, "hipMalloc");
+    n->stops_cap = st.size();
+  }
+  std::vector<double> sv(st.size()); std::vector<int32_t> so(st.size());
+  for (size_t i = 0; i < st.size(); ++i) { sv[i] = st[i].first; so[i] = st[i].second; }
+  if (hipMemcpy(n->stops_dev, sv.data(), sv.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(n->stop_out_dev, so.data(), so.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return pk_ctx_fail(c, PK_ERR_HIP, "hipMemcpy");
+  a.stops_p = n->stops_dev; a.stop_out_p = n->stop_out_dev;
+  return PK_OK;
+}
+
+// Tangent launch: B x ceil(K / KC) workgroups of the LDS kernel, or with plan.hbm a persistent grid over as many (candidate, chunk) items
+// on workspace slabs.  The context's scratch arena holds the column indices and, on slabs, behind them (whole 128-B lines) grid x slab;
+// status is OR-ed over the chunks, so it is zeroed first
+struct NetSensLaunch {
+  const pk::NetDev* d; const pk::NetSolveArgs* a; const NetSensReq* s; long long B;
+  int threads; size_t lds;                       // LDS route
+  int grid; size_t cols_bytes;                   // slabs
+};
+static hipError_t net_sens_launch(void* scratch, hipStream_t st, void* user) {
+  const NetSensLaunch& r = *(const NetSensLaunch*)user;
+  const NetSensReq& s = *r.s;
+  hipError_t e = hipMemcpyAsync(scratch, s.cols_host, (size_t)s.K * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && r.a->status) e = hipMemsetAsync(r.a->status, 0, (size_t)r.B * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  const pk::NetSensArgs sa{(const int32_t*)scratch, s.K, s.plan.KC, s.dY};
+  if (s.plan.hbm) return pk::launch_net_ws_sens(*r.d, *r.a, sa, s.score, r.B, r.grid, (double*)((char*)scratch + r.cols_bytes), st);
+  if (s.score) return pk::launch_net_lds_sens_score(*r.d, *r.a, sa, *s.score, r.B, r.threads, r.lds, st);
+  return pk::launch_net_lds_sens(*r.d, *r.a, sa, r.B, r.threads, r.lds, st);
+}
+static int net_simulate_sens(pk_ctx* c, pk_net* n, const pk::NetSolveArgs& a, const NetSensReq& s, int64_t B) {
+  const bool score = s.score != nullptr;
+  const int kcl = std::min(s.K, s.plan.KC), n_chunks = (s.K + s.plan.KC - 1) / s.plan.KC;
+  NetSensLaunch q{&n->d, &a, &s, (long long)B, s.plan.threads, 0, 0, 0};
+  if (!s.plan.hbm) {
+    q.lds = score ? pk::net_sens_score_lds_bytes(n->d, n->nnzT, kcl) : pk::net_sens_lds_bytes(n->d, n->nnzT, kcl);
+    return pk_ctx_scratch_launch(c, (size_t)s.K * sizeof(int32_t), net_sens_launch, &q);
+  }
+  q.cols_bytes = ((size_t)s.K * sizeof(int32_t) + 127) / 128 * 128;
+  if (pk::net_sens_ws_grid(n->d, score, (long long)B * n_chunks, &q.grid) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
+  return pk_ctx_scratch_launch(c, q.cols_bytes + (size_t)q.grid * pk::net_sens_ws_slab_doubles(n->d, kcl, score) * sizeof(double), net_sens_launch, &q);
+}
+
+// Every network launch.  `a`: zeroed, with the loss and measurement fields that `fl` reads filled in by the entry point (Y may be null for
+// every flavour but Plain); the rest is filled here.  `sens`: the columns of the two tangent flavours with their plan, else null
 static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                              const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps,
-                             const pk::NetSolveArgs* fused, const NetSensReq* sens = nullptr) {
+                             NetFlavour fl, pk::NetSolveArgs& a, const NetSensReq* sens = nullptr) {
   if (!c || !n) return PK_ERR_ARG;
   if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
   if (T < 1 || !t_host) return pk_ctx_fail(c, PK_ERR_ARG, "t must hold >= 1 time points (host pointer)");
   if (B == 0) return PK_OK;
-  if (!x || !y0 || (!Y && !fused && !sens)) return pk_ctx_fail(c, PK_ERR_ARG, "null pointer");
+  if (!x || !y0 || (!Y && fl == NetFlavour::Plain)) return pk_ctx_fail(c, PK_ERR_ARG, "null pointer");
   if (B > 0x7fffffffLL) return pk_ctx_fail(c, PK_ERR_ARG, "batch too large for one launch");
   if (n->d.model == 2 && n->max_sites > 16) return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "combinatorial topology: <= 16 sites per protein");
-  NetPlan plan = net_plan(n, opts_in);
+  pk_solver_opts o = net_opts(opts_in);
+  const NetPlan plan = sens ? sens->plan : pk::net_plan(net_facts(n), o, fl, 0, net_switches());
   if (plan.code != PK_OK) return pk_ctx_fail(c, plan.code, plan.refusal);
-  if (sens && plan.kernel != (sens->hbm ? NetKernel::Workspace : NetKernel::Lds))
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: the plan for these options is neither the general LDS kernel nor the "
-                                              "HBM-workspace kernel");
-  const bool rosw_fused = fused && fused->loss_ptr && !sens;
-  const bool measure = rosw_fused && fused->meas;
-  if (measure) {
-    if (plan.kernel == NetKernel::Reg || plan.kernel == NetKernel::CombReg)
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused measurement: not on the register-resident kernels; ask for the general LDS kernel "
-                                                "(opts->linsolve = PK_LINSOLVE_STRUCTURED, kernel = \"lds\" in Python) or PK_KERNEL_WORKSPACE");
-    if (plan.kernel != NetKernel::Lds && plan.kernel != NetKernel::Workspace)
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused measurement: the order-3 integrator only; ask for opts->method = PK_METHOD_ROS34PW2 (method = \"rosw\" in "
-                                                "Python) on the general LDS kernel or the workspace kernel, or call pk_network_simulate_batch + "
-                                                "pk_network_observables_batch");
-  }
-  if (rosw_fused) {
-    if (plan.kernel == NetKernel::Reg || plan.kernel == NetKernel::CombReg)
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective with PK_METHOD_ROS34PW2: not on the register-resident kernels; ask for the general LDS "
-                                                "kernel (opts->linsolve = PK_LINSOLVE_STRUCTURED, kernel = \"lds\" in Python) or PK_KERNEL_WORKSPACE");
-    if (plan.kernel != NetKernel::Lds && plan.kernel != NetKernel::Workspace)
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective on request: PK_METHOD_ROS34PW2 on the LDS or the workspace kernel only");
-    // the rna baseline (N doubles) comes on top of the LDS of a plain launch: past 160 KiB the workspace kernel takes over
-    if (plan.kernel == NetKernel::Lds && pk::net_solve_fused_lds_bytes(n->d, n->nnzT) > 160 * 1024) plan.kernel = NetKernel::Workspace;
-  }
   const bool dp5 = plan.kernel == NetKernel::DP5;
   for (int k = 1; k < T; ++k) if (!(t_host[k] > t_host[k - 1])) return pk_ctx_fail(c, PK_ERR_ARG, "t must be strictly increasing");
-  pk_solver_opts o;
-  if (opts_in) o = *opts_in; else pk_default_opts(&o);
   if (!(o.rtol > 0.0 && o.atol >= 0.0)) return pk_ctx_fail(c, PK_ERR_ARG, "rtol must be > 0 and atol >= 0");
   if (o.max_steps <= 0) o.max_steps = dp5 ? 2000000 : 1000000;      // solvers.py:294 max_steps = 2_000_000
-  // landing points: every output time after t[0] plus every bucket edge strictly inside (t[0], t[T-1])
-  std::vector<std::pair<double, int>> st;
-  for (int k = 1; k < T; ++k) st.push_back({t_host[k], k});
-  for (double gk : n->kin_grid_host) {
-    if (gk > t_host[0] && gk < t_host[T - 1]) {
-      bool dup = false;
-      for (int k = 1; k < T; ++k) if (t_host[k] == gk) { dup = true; break; }
-      if (!dup) st.push_back({gk, -1});
-    }
-  }
-  std::sort(st.begin(), st.end());
-  if (dp5) {                                        // the explicit integrator interpolates its outputs: it only needs the T output times
-    st.clear();
-    for (int k = 0; k < T; ++k) st.push_back({t_host[k], k});
-  }
-  pk::NetSolveArgs a;
-  std::memset(&a, 0, sizeof(a));
+  if (o.err_norm < PK_NORM_DEFAULT || o.err_norm > PK_NORM_RMS) return pk_ctx_fail(c, PK_ERR_ARG, "unknown opts->err_norm");
   a.x = x; a.x_is_raw = x_is_raw; a.y0 = y0; a.y0_batched = y0_is_batched ? 1 : 0; a.t0 = t_host[0]; a.T = T; a.Y = Y;
   a.status = status; a.n_steps = n_steps; a.rtol = o.rtol; a.atol = o.atol; a.h0 = o.h0; a.max_steps = o.max_steps;
-  if (o.err_norm < PK_NORM_DEFAULT || o.err_norm > PK_NORM_RMS) return pk_ctx_fail(c, PK_ERR_ARG, "unknown opts->err_norm");
   a.err_rms = (o.err_norm == PK_NORM_RMS) ? 1 : 0;
-  a.n_stops = (int)st.size();
-  if (fused) {
-    a.loss_obs = fused->loss_obs; a.loss_w = fused->loss_w; a.loss_defaults = fused->loss_defaults; a.loss_mode = fused->loss_mode;
-    a.loss_fail = fused->loss_fail; a.loss_sums = fused->loss_sums; a.loss_F = fused->loss_F; a.loss_rna_base = fused->loss_rna_base;
-    for (int k = 0; k < 4; ++k) a.loss_lam[k] = fused->loss_lam[k];
-    for (int k = 0; k < 3; ++k) a.loss_norm[k] = fused->loss_norm[k];
-    a.loss_ptr = fused->loss_ptr; a.loss_prot = fused->loss_prot; a.loss_site = fused->loss_site; a.loss_lobs = fused->loss_lobs; a.loss_lw = fused->loss_lw;
-    a.meas = fused->meas; a.meas_id = fused->meas_id; a.meas_n = fused->meas_n; a.meas_eps = fused->meas_eps;
-    a.meas_perm = fused->meas_perm; a.meas_pred = fused->meas_pred; a.meas_metric = fused->meas_metric;
-    if (!rosw_fused && !sens && !(plan.kernel == NetKernel::ArkPair && pk::net_arkp_fuses_loss()))
-      return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: topologies 0 / 1 / 4 on the default additive integrator only; "
-                                                "use pk_network_simulate_batch + pk_network_objective_batch");
-  }
   if (hipSetDevice(pk_ctx_device(c)) != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipSetDevice");
   hipStream_t stream = (hipStream_t)pk_ctx_stream(c);
-  if (st.size() <= 64) {
-    for (size_t i = 0; i < st.size(); ++i) { a.stops_v[i] = st[i].first; a.stop_out_v[i] = st[i].second; }
-  } else {
-    // long output grids: stage through a per-network device buffer (the previous launch on it must have finished)
-    std::lock_guard<std::mutex> g(n->mu);
-    if (hipDeviceSynchronize() != hipSuccess) return pk_ctx_fail(c, PK_ERR_HIP, "hipDeviceSynchronize");      // any stream of any context
-    if (n->stops_cap < st.size()) {
-      if (n->stops_dev) (void)hipFree(n->stops_dev);
-      if (n->stop_out_dev) (void)hipFree(n->stop_out_dev);
-      n->stops_dev = nullptr; n->stop_out_dev = nullptr; n->stops_cap = 0;
-      if (hipMalloc((void**)&n->stops_dev, st.size() * 8) != hipSuccess || hipMalloc((void**)&n->stop_out_dev, st.size() * 4) != hipSuccess)
-        return pk_ctx_fail(c, PK_ERR_NOMEM, "hipMalloc");
-      n->stops_cap = st.size();
-    }
-    std::vector<double> sv(st.size()); std::vector<int32_t> so(st.size());
-    for (size_t i = 0; i < st.size(); ++i) { sv[i] = st[i].first; so[i] = st[i].second; }
-    if (hipMemcpy(n->stops_dev, sv.data(), sv.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(n->stop_out_dev, so.data(), so.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return pk_ctx_fail(c, PK_ERR_HIP, "hipMemcpy");
-    a.stops_p = n->stops_dev; a.stop_out_p = n->stop_out_dev;
-  }
+  if (const int rc = net_landing_points(c, n, t_host, T, dp5, a)) return rc;
+  if (sens) return net_simulate_sens(c, n, a, *sens, B);
+  const bool measure = fl == NetFlavour::Measure, rosw_fused = measure || fl == NetFlavour::ScoreLists;
   const int M = n->d.model;
   switch (plan.kernel) {
     case NetKernel::Workspace: {
-      if (sens) {
-        // tangents on slabs: a persistent grid over the B x ceil(K / KC) (candidate, chunk) items.  The scratch arena holds the column
-        // indices (whole 128-B lines) and behind them grid x slab; status is OR-ed over the chunks, so it is zeroed first
-        const int kcl = std::min(sens->K, sens->KC), n_chunks = (sens->K + sens->KC - 1) / sens->KC;
-        const size_t cols_bytes = ((size_t)sens->K * sizeof(int32_t) + 127) / 128 * 128;
-        struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; const NetSensReq* s; long long B; int grid; size_t cols_bytes; int32_t* status; }
-            q{&n->d, &a, sens, (long long)B, 0, cols_bytes, status};
-        if (pk::net_sens_ws_grid(n->d, sens->score != nullptr, (long long)B * n_chunks, &q.grid) != hipSuccess)
-          return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
-        auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
-          const Q& r = *(const Q*)user;
-          hipError_t e = hipMemcpyAsync(scratch, r.s->cols_host, (size_t)r.s->K * sizeof(int32_t), hipMemcpyHostToDevice, s);
-          if (e == hipSuccess && r.status) e = hipMemsetAsync(r.status, 0, (size_t)r.B * sizeof(int32_t), s);
-          if (e != hipSuccess) return e;
-          const pk::NetSensArgs sa{(const int32_t*)scratch, r.s->K, r.s->KC, r.s->dY};
-          return pk::launch_net_ws_sens(*r.d, *r.a, sa, r.s->score, r.B, r.grid, (double*)((char*)scratch + r.cols_bytes), s);
-        };
-        const size_t slab = pk::net_sens_ws_slab_doubles(n->d, kcl, sens->score != nullptr);
-        return pk_ctx_scratch_launch(c, cols_bytes + (size_t)q.grid * slab * sizeof(double), launch, &q);
-      }
       // ROS34PW2 on workspace slabs (net_solve_ws_kernel): grid = min(B, resident workgroups), workspace = grid x slab of the scratch arena
-      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; bool fused, measure; } q{&n->d, &a, (long long)B, 0, rosw_fused, measure};
-      if ((measure ? pk::net_ws_measure_grid(n->d, (long long)B, &q.grid) : rosw_fused ? pk::net_ws_fused_grid(n->d, (long long)B, &q.grid)
-                                                                                      : pk::net_ws_grid(n->d, (long long)B, &q.grid)) != hipSuccess)
+      struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; long long B; int grid; decltype(&pk::launch_net_ws) launch; }
+          q{&n->d, &a, (long long)B, 0, measure ? pk::launch_net_ws_measure : rosw_fused ? pk::launch_net_ws_fused : pk::launch_net_ws};
+      if ((measure ? pk::net_ws_measure_grid : rosw_fused ? pk::net_ws_fused_grid : pk::net_ws_grid)(n->d, (long long)B, &q.grid) != hipSuccess)
         return pk_ctx_fail(c, PK_ERR_HIP, "occupancy query");
       auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
         const Q& r = *(const Q*)user;
-        return r.measure ? pk::launch_net_ws_measure(*r.d, *r.a, r.B, r.grid, (double*)scratch, s)
-               : r.fused ? pk::launch_net_ws_fused(*r.d, *r.a, r.B, r.grid, (double*)scratch, s)
-                         : pk::launch_net_ws(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
+        return r.launch(*r.d, *r.a, r.B, r.grid, (double*)scratch, s);
       };
       // a fused launch's slab is N doubles longer (the rna baseline), a measuring launch's too
       const size_t slab = rosw_fused ? pk::net_ws_fused_slab_doubles(n->d) : pk::net_ws_slab_doubles(n->d);
@@ -570,27 +529,7 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       break;
     }
     case NetKernel::Lds: {
-      // every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
-      int threads = (n->d.S <= 128 && n->d.N <= 64) ? 64 : 256;        // measured at S = 500: 256 threads beat 128 by 1.33x
-      if (const char* e = getenv("PK_NET_THREADS")) { const int v = atoi(e); if ((v == 64 || v == 128 || v == 256) && n->d.S <= 4 * v && n->d.N <= 2 * v) threads = v; }
-      if (sens) {
-        // B x ceil(K / KC) workgroups; the column indices go through the context's scratch arena; status is OR-ed over the chunks
-        const int kcl = std::min(sens->K, sens->KC);
-        if ((size_t)kcl * n->d.S > 512) threads = 256;
-        struct Q { const pk::NetDev* d; const pk::NetSolveArgs* a; const NetSensReq* s; long long B; int threads; size_t lds; int32_t* status; }
-            q{&n->d, &a, sens, (long long)B, threads,
-              sens->score ? pk::net_sens_score_lds_bytes(n->d, n->nnzT, kcl) : pk::net_sens_lds_bytes(n->d, n->nnzT, kcl), status};
-        auto launch = [](void* scratch, hipStream_t s, void* user) -> hipError_t {
-          const Q& r = *(const Q*)user;
-          hipError_t e = hipMemcpyAsync(scratch, r.s->cols_host, (size_t)r.s->K * sizeof(int32_t), hipMemcpyHostToDevice, s);
-          if (e == hipSuccess && r.status) e = hipMemsetAsync(r.status, 0, (size_t)r.B * sizeof(int32_t), s);
-          if (e != hipSuccess) return e;
-          const pk::NetSensArgs sa{(const int32_t*)scratch, r.s->K, r.s->KC, r.s->dY};
-          if (r.s->score) return pk::launch_net_lds_sens_score(*r.d, *r.a, sa, *r.s->score, r.B, r.threads, r.lds, s);
-          return pk::launch_net_lds_sens(*r.d, *r.a, sa, r.B, r.threads, r.lds, s);
-        };
-        return pk_ctx_scratch_launch(c, (size_t)sens->K * sizeof(int32_t), launch, &q);
-      }
+      const int threads = plan.threads;              // every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
       if (rosw_fused) {
         const size_t lb = pk::net_solve_fused_lds_bytes(n->d, n->nnzT);
         const hipError_t ef = measure ? pk::launch_net_lds_measure(n->d, a, (long long)B, threads, lb, stream)
@@ -620,7 +559,16 @@ int64_t pk_network_workspace_bytes(pk_ctx* c, const pk_net* n, int64_t B) {
 
 int pk_network_simulate_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, int x_is_raw, const double* y0, int y0_is_batched,
                               const double* t_host, int T, const pk_solver_opts* opts_in, double* Y, int32_t* status, int32_t* n_steps) {
-  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts_in, Y, status, n_steps, nullptr);
+  pk::NetSolveArgs a;
+  std::memset(&a, 0, sizeof(a));
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts_in, Y, status, n_steps, NetFlavour::Plain, a);
+}
+
+// the caller's scoring arguments of the two loss entry points; without lambdas the three objectives weigh 1 and the prior 0
+static void net_fill_loss(pk::NetSolveArgs& f, int loss_mode, const double* defaults, const double* lambdas, double fail_value, double* loss_sums,
+                          double* F) {
+  f.loss_defaults = defaults; f.loss_mode = loss_mode; f.loss_fail = fail_value; f.loss_sums = loss_sums; f.loss_F = F;
+  for (int k = 0; k < 4; ++k) f.loss_lam[k] = lambdas ? lambdas[k] : k < 3 ? 1.0 : 0.0;
 }
 
 // simulate + three-objective loss in ONE launch (SURVEY fused op (i), VERDICT r2 item 4 iii): the integrator scores the observations of the
@@ -644,7 +592,8 @@ int pk_network_simulate_objective_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_
   pk::NetSolveArgs f;
   std::memset(&f, 0, sizeof(f));
   int Tl = 0;
-  if (opts && (opts->method == PK_METHOD_ROS34PW2 || opts->kernel == PK_KERNEL_WORKSPACE)) {
+  const bool lists = opts && (opts->method == PK_METHOD_ROS34PW2 || opts->kernel == PK_KERNEL_WORKSPACE);
+  if (lists) {
     if (!pk_loss_fused_lists(l, &f.loss_ptr, &f.loss_prot, &f.loss_site, &f.loss_lobs, &f.loss_lw, f.loss_norm, &Tl, &f.loss_rna_base))
       return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: protein / phospho baselines must be time index 0 and rna observations not earlier "
                                                 "than the rna baseline");
@@ -652,10 +601,9 @@ int pk_network_simulate_objective_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_
     return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "fused objective: protein / phospho baselines must be time index 0, rna observations not earlier than "
                                               "the rna baseline, and no (state, time) observed twice");
   if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the loss data were created for");
-  f.loss_defaults = defaults; f.loss_mode = loss_mode; f.loss_fail = fail_value; f.loss_sums = loss_sums; f.loss_F = F;
-  f.loss_lam[0] = lambdas ? lambdas[0] : 1.0; f.loss_lam[1] = lambdas ? lambdas[1] : 1.0; f.loss_lam[2] = lambdas ? lambdas[2] : 1.0;
-  f.loss_lam[3] = lambdas ? lambdas[3] : 0.0;
-  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps, &f);
+  net_fill_loss(f, loss_mode, defaults, lambdas, fail_value, loss_sums, F);
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps,
+                           lists ? NetFlavour::ScoreLists : NetFlavour::ScoreTables, f);
 }
 
 // simulate + fold-change observables + scalar Morris metric in ONE launch (SURVEY fused op (iii) on the network path; the reference's
@@ -679,19 +627,11 @@ int pk_network_simulate_measure_batch(pk_ctx* c, pk_net* n, pk_loss* l, int64_t 
                                               "the rna baseline; call pk_network_simulate_batch + pk_network_observables_batch");
   if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the index lists were created for");
   f.meas = 1; f.meas_id = metric_id; f.meas_eps = eps; f.meas_pred = pred; f.meas_metric = metric;
-  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps, &f);
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, opts, Y, status, n_steps, NetFlavour::Measure, f);
 }
 
-// Columns one workgroup of the sensitivity kernel carries on this network: the largest count whose LDS request (net_sens_lds_bytes) stays
-// within 160 KiB, at most n_var; 0 where not even one fits or the network is beyond the LDS kernel's thread layout.  Host arithmetic only
-// (dev knob PK_NET_SENS_KC: a smaller count, read at every call)
-int pk_network_sens_columns_per_launch(pk_net* n) {
-  if (!n) return PK_ERR_ARG;
-  if (n->d.S > 1024 || n->d.N > 512) return 0;
-  int kc = std::min(pk::net_sens_max_columns(n->d, n->nnzT, 160 * 1024), n->d.n_var);
-  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < kc) kc = v; }
-  return kc;
-}
+int pk_network_sens_columns_per_launch(pk_net* n) { return n ? net_sens_lds_columns(n, false) : PK_ERR_ARG; }
+int pk_network_objective_grad_columns_per_launch(pk_net* n) { return n ? net_sens_lds_columns(n, true) : PK_ERR_ARG; }
 
 // Columns one work item of the slab route carries: min(K, n_var, W), W = 16 (DESIGN 5.9 records the measurement behind it); the dev knob
 // PK_NET_SENS_KC lowers W as it lowers the LDS counts (read at every call).  The width is the same for both flavours: `scoring` is part of
@@ -699,9 +639,7 @@ int pk_network_sens_columns_per_launch(pk_net* n) {
 int pk_network_sens_hbm_columns(pk_net* n, int K, int scoring) {
   if (!n || K < 0) return PK_ERR_ARG;
   (void)scoring;
-  int W = 16;
-  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < W) W = v; }
-  return std::min(std::min(K, n->d.n_var), W);
+  return pk::net_sens_hbm_columns(K, n->d.n_var, net_switches().sens_hbm_width);
 }
 
 // Bytes of slabs a launch of the slab route reserves: grid x slab, grid = min(B x chunks, resident workgroups of the flavour's kernel) -- bounded
@@ -718,6 +656,18 @@ int64_t pk_network_sens_workspace_bytes(pk_ctx* c, pk_net* n, int64_t B, int K, 
   return (int64_t)grid * (int64_t)(pk::net_sens_ws_slab_doubles(n->d, kc, scoring != 0) * sizeof(double));
 }
 
+// cols (HOST pointer, not null) names K distinct parameters
+static int net_check_cols(pk_ctx* c, const pk_net* n, const int32_t* cols_host, int K) {
+  std::vector<char> seen((size_t)n->d.n_var, 0);
+  for (int k = 0; k < K; ++k) {
+    const int col = cols_host[k];
+    if (col < 0 || col >= n->d.n_var) return pk_ctx_fail(c, PK_ERR_ARG, "cols: index outside [0, n_var)");
+    if (seen[col]) return pk_ctx_fail(c, PK_ERR_ARG, "cols: an index is repeated");
+    seen[col] = 1;
+  }
+  return PK_OK;
+}
+
 // Y and dY / dx[cols] from one integration of the augmented system (pk_network_sens.hpp).  Always the order-3 method: on the general LDS
 // kernel where a column fits beside the state, else -- and with PK_KERNEL_HBM -- on HBM slabs.  K = 0 is pk_network_simulate_batch on the
 // general LDS kernel (PK_KERNEL_HBM: on the workspace kernel)
@@ -727,45 +677,19 @@ int pk_network_simulate_sens_batch(pk_ctx* c, pk_net* n, int64_t B, const double
   if (!c || !n) return PK_ERR_ARG;
   if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
   if (K < 0) return pk_ctx_fail(c, PK_ERR_ARG, "K must be >= 0");
-  if (opts && (opts->method == PK_METHOD_ARK436 || opts->method == PK_METHOD_DP5))
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities integrate with PK_METHOD_ROS34PW2 only: leave opts->method at its default or ask for "
-                                              "PK_METHOD_ROS34PW2");
-  if (opts && opts->kernel == PK_KERNEL_WORKSPACE)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "network sensitivities: PK_KERNEL_WORKSPACE names the state kernel; leave opts->kernel at PK_KERNEL_AUTO, or "
-                                              "ask for the tangents on HBM slabs with PK_KERNEL_HBM");
+  const pk_solver_opts asked = net_opts(opts), o = pk::net_tangent_opts(asked);
+  const NetSensReq req{cols_host, K, dY, nullptr, pk::net_plan(net_facts(n), asked, NetFlavour::Sens, K, net_switches())};
+  if (req.plan.code != PK_OK) return pk_ctx_fail(c, req.plan.code, req.plan.refusal);
   if (K > 0) {
     if (!cols_host) return pk_ctx_fail(c, PK_ERR_ARG, "cols is NULL with K > 0");
     if (!dY) return pk_ctx_fail(c, PK_ERR_ARG, "dY is NULL with K > 0");
-    std::vector<char> seen((size_t)n->d.n_var, 0);
-    for (int k = 0; k < K; ++k) {
-      const int col = cols_host[k];
-      if (col < 0 || col >= n->d.n_var) return pk_ctx_fail(c, PK_ERR_ARG, "cols: index outside [0, n_var)");
-      if (seen[col]) return pk_ctx_fail(c, PK_ERR_ARG, "cols: an index is repeated");
-      seen[col] = 1;
-    }
+    if (const int rc = net_check_cols(c, n, cols_host, K)) return rc;
   } else if (!Y && B > 0) return pk_ctx_fail(c, PK_ERR_ARG, "K = 0 and Y is NULL: nothing to compute");
   if (B == 0) return PK_OK;
-  pk_solver_opts o;
-  if (opts) o = *opts; else pk_default_opts(&o);
-  const bool hbm_asked = o.kernel == PK_KERNEL_HBM;
-  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = hbm_asked ? PK_KERNEL_WORKSPACE : PK_KERNEL_AUTO;
-  if (K == 0) return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr);
-  // the LDS kernel where a column fits beside the state; the slabs on request and wherever it does not
-  int KC = hbm_asked ? 0 : pk_network_sens_columns_per_launch(n);
-  const bool hbm = KC < 1;
-  if (hbm) { KC = pk_network_sens_hbm_columns(n, K, 0); o.kernel = PK_KERNEL_WORKSPACE; }
-  const NetSensReq req{cols_host, K, KC, dY, nullptr, hbm};
-  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, nullptr, &req);
-}
-
-// Columns one workgroup of the scoring flavour carries: as pk_network_sens_columns_per_launch with net_sens_score_lds_bytes (the rna
-// baseline, its tangents and the accumulators come on top): same 160 KiB, same n_var cap, same dev knob
-int pk_network_objective_grad_columns_per_launch(pk_net* n) {
-  if (!n) return PK_ERR_ARG;
-  if (n->d.S > 1024 || n->d.N > 512) return 0;
-  int kc = std::min(pk::net_sens_score_max_columns(n->d, n->nnzT, 160 * 1024), n->d.n_var);
-  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < kc) kc = v; }
-  return kc;
+  pk::NetSolveArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (K == 0) return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, NetFlavour::Plain, a);
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, NetFlavour::Sens, a, &req);
 }
 
 // The three objectives AND their derivative with respect to x[cols] from one integration of the augmented system: the scoring flavour of
@@ -781,12 +705,10 @@ int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, i
   if (!c || !n || !l) return PK_ERR_ARG;
   if (B < 0) return pk_ctx_fail(c, PK_ERR_ARG, "B must be >= 0");
   if (K < 0) return pk_ctx_fail(c, PK_ERR_ARG, "K must be >= 0");
-  if (opts && (opts->method == PK_METHOD_ARK436 || opts->method == PK_METHOD_DP5))
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients integrate with PK_METHOD_ROS34PW2 only: leave opts->method at its default or ask for "
-                                              "PK_METHOD_ROS34PW2");
-  if (opts && opts->kernel == PK_KERNEL_WORKSPACE)
-    return pk_ctx_fail(c, PK_ERR_UNSUPPORTED, "objective gradients: PK_KERNEL_WORKSPACE names the state kernel; leave opts->kernel at PK_KERNEL_AUTO, or "
-                                              "ask for the tangents on HBM slabs with PK_KERNEL_HBM");
+  const pk_solver_opts asked = net_opts(opts), o = pk::net_tangent_opts(asked);
+  const pk::NetSensScoreArgs sc{dpred, dsums, dF};
+  const NetSensReq req{cols_host, K, dY, &sc, pk::net_plan(net_facts(n), asked, NetFlavour::SensScore, K, net_switches())};
+  if (req.plan.code != PK_OK) return pk_ctx_fail(c, req.plan.code, req.plan.refusal);
   if (loss_mode < 0 || loss_mode > 7) return pk_ctx_fail(c, PK_ERR_ARG, "loss_mode must be 0..7");
   if (!Y && !dY && !pred && !dpred && !loss_sums && !dsums && !F && !dF)
     return pk_ctx_fail(c, PK_ERR_ARG, "every output pointer is NULL: pass at least one of Y, dY, pred, dpred, loss_sums, dsums, F, dF");
@@ -795,18 +717,8 @@ int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, i
   if ((F || dF) && !lambdas) return pk_ctx_fail(c, PK_ERR_ARG, "lambdas (protein, rna, phospho, prior) are required for F and dF");
   if (K > 0) {
     if (!cols_host) return pk_ctx_fail(c, PK_ERR_ARG, "cols is NULL with K > 0");
-    std::vector<char> seen((size_t)n->d.n_var, 0);
-    for (int k = 0; k < K; ++k) {
-      const int col = cols_host[k];
-      if (col < 0 || col >= n->d.n_var) return pk_ctx_fail(c, PK_ERR_ARG, "cols: index outside [0, n_var)");
-      if (seen[col]) return pk_ctx_fail(c, PK_ERR_ARG, "cols: an index is repeated");
-      seen[col] = 1;
-    }
+    if (const int rc = net_check_cols(c, n, cols_host, K)) return rc;
   }
-  pk_solver_opts o;
-  if (opts) o = *opts; else pk_default_opts(&o);
-  const bool hbm_asked = o.kernel == PK_KERNEL_HBM;
-  o.method = PK_METHOD_ROS34PW2; o.linsolve = PK_LINSOLVE_STRUCTURED; o.kernel = hbm_asked ? PK_KERNEL_WORKSPACE : PK_KERNEL_AUTO;
   if (K == 0) {
     if (pred || (!loss_sums && !F))
       return pk_ctx_fail(c, PK_ERR_ARG, "K = 0 computes loss_sums / F (and Y) as pk_network_simulate_objective_batch does: pass one of them, and ask "
@@ -824,16 +736,9 @@ int pk_network_simulate_objective_grad_batch(pk_ctx* c, pk_net* n, pk_loss* l, i
                                               "than the rna baseline; difference pk_network_simulate_batch + pk_network_objective_batch");
   if (Tl != T) return pk_ctx_fail(c, PK_ERR_ARG, "T differs from the grid the loss data were created for");
   if (B == 0) return PK_OK;
-  int KC = hbm_asked ? 0 : pk_network_objective_grad_columns_per_launch(n);
-  const bool hbm = KC < 1;
-  if (hbm) { KC = pk_network_sens_hbm_columns(n, K, 1); o.kernel = PK_KERNEL_WORKSPACE; }
-  f.loss_defaults = defaults; f.loss_mode = loss_mode; f.loss_fail = fail_value; f.loss_sums = loss_sums; f.loss_F = F;
-  f.loss_lam[0] = lambdas ? lambdas[0] : 1.0; f.loss_lam[1] = lambdas ? lambdas[1] : 1.0; f.loss_lam[2] = lambdas ? lambdas[2] : 1.0;
-  f.loss_lam[3] = lambdas ? lambdas[3] : 0.0;
+  net_fill_loss(f, loss_mode, defaults, lambdas, fail_value, loss_sums, F);
   f.meas_pred = pred;
-  const pk::NetSensScoreArgs sc{dpred, dsums, dF};
-  const NetSensReq req{cols_host, K, KC, dY, &sc, hbm};
-  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, &f, &req);
+  return net_simulate_impl(c, n, B, x, x_is_raw, y0, y0_is_batched, t_host, T, &o, Y, status, n_steps, NetFlavour::SensScore, f, &req);
 }
 
 int pk_network_unpack_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x_raw, double* x_phys) {
