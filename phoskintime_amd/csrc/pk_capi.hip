@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include "../../include/phoskin.h"
+#include "pk_env.hpp"
 #include "pk_launch.hpp"
 #include "pk_plan.hpp"
 #include "pk_sens_out.hpp"
@@ -90,31 +91,16 @@ int check_model(pk_ctx* c, int model, int n_sites) {
   return PK_OK;
 }
 
-// The environment switches of the per-protein selection (pk_plan.hpp), read once per process.
-const pk::ProteinSwitches& protein_switches() {
-  static const pk::ProteinSwitches once = [] {
-    pk::ProteinSwitches s;
-    const auto read = [](const char* name, int& value) { if (const char* v = getenv(name)) value = atoi(v); };
-    // PK_WIDE_RAND_EXACT picks among the exact kernels and the approximate one at randmod n = 7 / 8 -- the tests hold them to agreement:
-    //   1 (default)  parity elimination: the odd-popcount block of M is diagonal, the even Schur complement (64 x 64 at n = 7, 128 x 128
-    //                at n = 8) is inverted in registers (pk_rand_parity.hpp)
-    //   2            n = 7: the full 128 x 128 inverse in registers (pk_rand_dense.hpp, round 2's kernel); n = 8: block elimination over
-    //                the popcount levels with the Schur complements in LDS (pk_rand_level.hpp)
-    //   0            the n-cube kernel (approximate factorisation), which stays the path for n >= 9
-    read("PK_WIDE_RAND_EXACT", s.wide_rand_exact);
-    // A/B switch of the tests: PK_RAND_LEVEL6=1 runs randmod n = 6 on the level-block kernel instead of the one-wave kernel
-    read("PK_RAND_LEVEL6", s.rand_level6);
-    // [r3] randmod n = 6 with the default method: parity elimination in ONE wave per replica (pk_rand_parity.hpp, 8 x 8 lanes over the 32 x 32
-    // even Schur complement): 2.1-2.2 M replicas/s against 0.59 M of the 64 x 64 in-register inverse of pk_rand_fast.hpp (same box, B = 16 384 ... 65 536).
-    // PK_RAND_PARITY56: 0 = the old kernel, 1 = also n = 5 (dev; 4 x 4 lanes per replica, four replicas per wave: 9.1-10.2 M against 8.2-9.4 M of the 32-lane kernel at B >= 16 384,
-    // but 0.63 against 0.44 ms per launch at B = 7 -- not worth a second default; one wave per replica: 5.2-5.8 M)
-    read("PK_RAND_PARITY56", s.rand_parity56);
-    // PK_TPR=0 / 1 pins the lane-group / the thread-per-replica family for dev A/B runs, as opts->kernel does for callers
-    read("PK_TPR", s.tpr);
-    s.dist_sched = pk::dist_sched_env();
-    return s;
-  }();
-  return once;
+// The environment switches of the per-protein selection (pk_plan.hpp), out of the snapshot (pk_env.hpp).  What rand_parity56 was
+// measured for, [r3]: randmod n = 6 with the default method by parity elimination in ONE wave per replica (pk_rand_parity.hpp, 8 x 8 lanes
+// over the 32 x 32 even Schur complement) runs 2.1-2.2 M replicas/s against 0.59 M of the 64 x 64 in-register inverse of pk_rand_fast.hpp
+// (same box, B = 16 384 ... 65 536).  n = 5 there (4 x 4 lanes per replica, four replicas per wave): 9.1-10.2 M against 8.2-9.4 M of the
+// 32-lane kernel at B >= 16 384, but 0.63 against 0.44 ms per launch at B = 7 -- not worth a second default; one wave per replica: 5.2-5.8 M
+pk::ProteinSwitches protein_switches() {
+  const pk::Env& e = pk::env();
+  pk::ProteinSwitches s;
+  s.wide_rand_exact = e.wide_rand_exact; s.rand_level6 = e.rand_level6; s.rand_parity56 = e.rand_parity56; s.tpr = e.tpr; s.dist_sched = e.dist_sched;
+  return s;
 }
 
 // Copy or default the options; a max_steps that is not positive means the default.

@@ -34,6 +34,7 @@
 // dR/dt = A - B R ; dP/dt = C R - (D + sum S_i) P + sum X_i ; dX_i/dt = S_i P - (1 + D_i) X_i
 #pragma once
 #include "pk_dist_rows.hpp"
+#include "pk_env.hpp"
 
 namespace pk {
 
@@ -120,7 +121,7 @@ constexpr size_t dist_fast_lds_bytes() { return PARK ? (size_t)(dist_fast_slots<
 //   LEVEL  every other wave takes its priority from its own progress, the output index k of its slowest live replica: 2 before output
 //          PK_DSCHED_K2, 1 before PK_DSCHED_K1, 0 from there on (4 + 4 + 5 of the benchmark's 13 intervals), re-evaluated at the top of
 //          each step.  Two v_cmp on the lanes' k feed the scalar unit, which does the rest; with the policy off a uniform branch skips them.
-enum { PK_DSCHED_OFF = 0, PK_DSCHED_LEAD_SLOT = 1, PK_DSCHED_LEVEL = 2, PK_DSCHED_LEAD_BLOCK = 4 };
+// The PK_DSCHED_* bits of the policies live with the parser of the switch that names them (pk_env.hpp).
 constexpr int PK_DSCHED_K2 = 5, PK_DSCHED_K1 = 9;
 // s_getreg operands: id | offset << 6 | (size - 1) << 11.  HW_ID (register 4): wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]
 constexpr int PK_HWREG_HW_ID = 4 | (31 << 11), PK_HWREG_HW_ID_WAVE = 4 | (3 << 11), PK_HWREG_XCC_ID = 20 | (31 << 11);

@@ -7,14 +7,6 @@
 
 namespace pk {
 
-// PK_DIST_SCHED (read once per process): the wave-pacing policy of the parked one-wave kernels as PK_DSCHED_* bits (pk_dist_fast.hpp).
-// dist_sched_parse names the accepted values and returns -1 for anything else; the C entry points reject such a setting before a launch.
-// dist_sched_env: the parsed setting, PK_DSCHED_UNSET without one (the launch table's own choice applies).
-constexpr int PK_DSCHED_UNSET = 0x100;
-int dist_sched_parse(const char* v);
-int dist_sched_env();
-extern const char* const kDistSchedNames;
-
 // One instantiation: NT threads per workgroup, launch-uniform choices CFG, shadowed or resident rows (pk_dist_fast.hpp).
 template <int G, int RPL, bool PARK, int NT, class CFG, bool RES, int TRACE = 0>
 static void launch_cfg(const SolveArgs& a, hipStream_t st) {
@@ -44,8 +36,9 @@ static void launch_cfg(const SolveArgs& a, hipStream_t st) {
     SolveArgs b = a;
     // unset: what was measured.  Pacing pays while a SIMD gets at most one wave beyond its resident ones -- a grid of up
     // to 4/3 of the resident capacity, the benchmark's 4 096 workgroups on 3 072 slots among them -- in the four-lane layouts; larger
-    // grids and the eight-lane layouts, which it slowed, run unpaced.  A setting of PK_DIST_SCHED applies to every grid (A/B runs)
-    const int env = dist_sched_env();
+    // grids and the eight-lane layouts, which it slowed, run unpaced.  A setting of PK_DIST_SCHED applies to every grid (A/B runs); one that
+    // names no policy, which the C entry points refuse before a launch (pk_capi.hip), runs unpaced if it gets here all the same
+    const int env = pk::env().dist_sched;
     const bool pays = G == 4 && nblk <= (long long)resident + resident / 3;
     b.sched = env == PK_DSCHED_UNSET ? (pays ? PK_DSCHED_LEAD_SLOT | PK_DSCHED_LEVEL : PK_DSCHED_OFF) : env < 0 ? (int)PK_DSCHED_OFF : env;
     b.R1 = resident;
@@ -65,13 +58,11 @@ static void launch_nt(const SolveArgs& a, hipStream_t st) {
   else launch_cfg<G, RPL, PARK, NT, DistAny, RES>(a, st);
 }
 
-// PK_DIST_LAYOUT (dev A/B, read once per process; any other word, or none, is no override):
+// PK_DIST_LAYOUT (dev A/B; DistLayoutEnv of pk_env.hpp):
 //   8x4     forces the register-only, shadowed 8 x 4 layout for 17 <= n <= 32;
 //   wg256   runs the 4 x 8 parked layout in 256-thread workgroups;
 //   shadow  keeps the shadowed layout at every n.
-enum DistLayoutEnv { PK_DLAYOUT_NONE = 0, PK_DLAYOUT_8X4, PK_DLAYOUT_WG256, PK_DLAYOUT_SHADOW };
-DistLayoutEnv dist_layout_env();
-
+//
 // The LRP12 layout table: G lanes per replica x RPL rows per lane for the slots a replica needs -- its n sites, and R and P as well in the
 // resident layout -- with as few idle slots as possible.
 //   * G = 4 up to 32 slots, 8 above: fewer lanes per replica = fewer DPP reduction levels per solve (and, shadowed, less redundant work on

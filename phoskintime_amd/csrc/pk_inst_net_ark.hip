@@ -1,7 +1,7 @@
 // Instantiations + launcher of the order-4 network integrator (pk_network_solve_ark.hpp): topologies 0 / 1 / 4, site classes 4 / 6 / 8.
 #include "pk_network_solve_ark.hpp"
 #include <atomic>
-#include <cstdlib>
+#include "pk_env.hpp"
 
 namespace pk {
 
@@ -10,9 +10,8 @@ static int site_class(int max_sites) { return max_sites <= 4 ? 4 : max_sites <= 
 // rows of a block vector: 2 + site class (topologies 0 / 1 / 4), 1 + 2^NB with NB = 2 or 3 (combinatorial)
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads) {
   const int rows = n.model == 2 ? 1 + (max_sites <= 2 ? 4 : 8) : 2 + site_class(max_sites);
-  // PK_ARK_LDS_PAD (bytes, dev switch, read once): unused LDS per workgroup, to measure the kernel at fewer resident workgroups per CU
-  static const size_t pad = [] { const char* v = getenv("PK_ARK_LDS_PAD"); return v ? (size_t)atol(v) : (size_t)0; }();
-  return net_solve_ark_lds_bytes(n, nnzT, rows, threads) + pad;
+  // PK_ARK_LDS_PAD (bytes, dev switch): unused LDS per workgroup, to measure the kernel at fewer resident workgroups per CU
+  return net_solve_ark_lds_bytes(n, nnzT, rows, threads) + env().ark_lds_pad;
 }
 
 template <int M, int MS>
@@ -53,8 +52,8 @@ static hipError_t launch_comb(const NetDev& n, const NetSolveArgs& a, long long 
 
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st) {
   if (n.model == 2) {
-    // PK_ARK2_EXACT=0 (read once): round 2's approximate factorisation as the implicit operator (the A/B twin of the exact block solve)
-    static const bool exact = [] { const char* v = getenv("PK_ARK2_EXACT"); return !(v && v[0] == '0'); }();
+    // PK_ARK2_EXACT=0: round 2's approximate factorisation as the implicit operator (the A/B twin of the exact block solve)
+    const bool exact = env().ark2_exact;
     if (max_sites <= 2) return exact ? launch_comb<2, true>(n, a, B, threads, lds, st) : launch_comb<2, false>(n, a, B, threads, lds, st);
     return exact ? launch_comb<3, true>(n, a, B, threads, lds, st) : launch_comb<3, false>(n, a, B, threads, lds, st);
   }

@@ -2,24 +2,18 @@
 // arrow topologies 0 / 4 (here) and the sequential chain 1 (pk_inst_net_arkc.hip), site classes 4 / 6 / 8 (3 / 4 / 5 rows per lane).
 #include <type_traits>
 #include "pk_network_solve_arkp.hpp"
-#include <cstdlib>
+#include "pk_env.hpp"
 
 namespace pk {
 
-bool net_arkp_enabled() {
-  static const bool on = [] { const char* v = getenv("PK_ARK_PAIR"); return !(v && v[0] == '0'); }();
-  return on;
-}
+bool net_arkp_enabled() { return env().ark_pair.enabled; }
 
 // the sequential chain's instantiations live in their own translation unit (pk_inst_net_arkc.hip: parallel hipcc)
 hipError_t launch_net_arkp_chain(const NetDev& n, const NetSolveArgs& a, int threads, size_t lds, bool park, int nrl, long long B, hipStream_t st);
 
 // PK_ARK_PAIR: 0 = round 2's kernel (one thread per protein), 1 = the pair layout out of registers (256 VGPRs, 2 waves / SIMD),
 // 3 = the pair layout on the register diet (168 VGPRs, 3 waves / SIMD)
-static int arkp_mode() {
-  static const int m = [] { const char* v = getenv("PK_ARK_PAIR"); return v ? atoi(v) : 3; }();
-  return m;
-}
+static int arkp_mode() { return env().ark_pair.mode; }
 
 bool net_arkp_fuses_loss() { return arkp_mode() == 3; }
 

@@ -1,7 +1,6 @@
 // Instantiations + launcher of the random-model throughput kernel (pk_rand_fast.hpp).
 #include "pk_rand_fast.hpp"
-#include <cstring>
-#include <cstdlib>
+#include "pk_env.hpp"
 #include "pk_launch.hpp"
 
 namespace pk {
@@ -24,8 +23,7 @@ void launch_rand_fast6_rodas4(const SolveArgs& a, hipStream_t st);
 
 void launch_rand_fast(const SolveArgs& a, int method, hipStream_t st) {
   // dev A/B: PK_RAND_ROWS=1 keeps the one-row-per-lane kernels for n = 3, 4
-  static const bool one_row = getenv("PK_RAND_ROWS") && !strcmp(getenv("PK_RAND_ROWS"), "1");
-  if (!one_row && (a.n_sites == 3 || a.n_sites == 4)) { launch_rand_fastr(a, method, st); return; }
+  if (!env().rand_one_row && (a.n_sites == 3 || a.n_sites == 4)) { launch_rand_fastr(a, method, st); return; }
   switch (a.n_sites) {
     case 1: launch_nb<1>(a, method, st); break;
     case 2: launch_nb<2>(a, method, st); break;

@@ -1,9 +1,9 @@
 // Instantiations + launcher of the thread-per-replica kernels (pk_tpr.hpp): LRP12 only (the default method).
 #include "pk_tpr.hpp"
 #include "pk_tpr_rand.hpp"
+#include "pk_env.hpp"
 #include "pk_launch.hpp"
 #include <atomic>
-#include <cstdlib>
 
 namespace pk {
 
@@ -26,15 +26,12 @@ static hipError_t launch_tpr_one(const SolveArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((tpr_kernel<MODEL, NS, PK_METHOD_LRP12, STAGE>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return hipSuccess;
 }
-// PK_TPR_STAGE=1 (read once): trajectories of the smallest systems go through the thread-private line buffer (pk_tpr.hpp, STAGE).
+// PK_TPR_STAGE=1: trajectories of the smallest systems go through the thread-private line buffer (pk_tpr.hpp, STAGE).
 // Measured at distmod n = 4, B = 524 288 (profiles/r03_d_tpr_*): staged WRITE_SIZE = 1.001 x the algorithmic bytes at 0.597 ms per launch;
 // direct 16-byte stores 1.35 x at 0.499 ms (round 2's 8-byte stores: 1.44 x, 0.512 ms).  The kernel is bound by VALU issue, not by HBM (14 % of
 // peak), and the buffer's 32 KB of LDS cost an occupancy step (3 -> 2 workgroups per CU): the faster path is the default, the lean one
 // is there for callers who share the HBM with something that needs it.
-static bool tpr_stage(const SolveArgs& a) {
-  static const bool on = [] { const char* v = getenv("PK_TPR_STAGE"); return v && v[0] == '1'; }();
-  return on && a.sol != nullptr;
-}
+static bool tpr_stage(const SolveArgs& a) { return env().tpr_stage && a.sol != nullptr; }
 
 template <int NB>
 static hipError_t launch_tpr_rand(const SolveArgs& a, hipStream_t st) {

@@ -22,10 +22,7 @@ PK_DECL(2, 8) PK_DECL(2, 16) PK_DECL(2, 32) PK_DECL(2, 64)
 
 // distributive-model throughput kernel (pk_dist_fast.hpp): RODAS4, arrow elimination, 4-16 lanes per replica
 void launch_dist_fast(const SolveArgs&, int method, hipStream_t);
-// wave pacing of its parked LRP12 kernels and the wave timeline of the traced build (pk_dist_fast12.hpp)
-int dist_sched_parse(const char* v);                               // PK_DSCHED_* bits, -1 for a value that is none of kDistSchedNames
-int dist_sched_env();                                              // PK_DIST_SCHED, parsed once per process: -1 for no policy, 0x100 when unset
-extern const char* const kDistSchedNames;
+// the wave timeline of the traced build of its parked LRP12 kernels (pk_dist_fast12.hpp)
 hipError_t dist_trace_set(void* records, long long capacity);
 // random-model throughput kernel (pk_rand_fast.hpp): RODAS4 / LRP8, in-register Gauss-Jordan on the 2^n coupled rows
 void launch_rand_fast(const SolveArgs&, int method, hipStream_t);

@@ -12,6 +12,7 @@
 #include "pk_network_rk45.hpp"
 #include "pk_network_sens.hpp"
 #include "pk_net_plan.hpp"
+#include "pk_env.hpp"
 namespace pk {
 // persistent grid: min(B, workgroups of `kernel` at `threads` each resident on the current device at once)
 hipError_t net_persistent_grid(const void* kernel, int threads, long long B, int* grid);
@@ -315,14 +316,9 @@ int pk_network_jacobian_batch(pk_ctx* c, pk_net* n, int64_t B, const double* x, 
 
 // Which kernel a network launch runs, with which method, or why not: net_plan of pk_net_plan.hpp, the single source of truth for every
 // flavour (the Python host layer picks its default tolerances from the method).  Here: what the plan is told about this network
-// (net_facts) and about the environment (net_switches), both read at every call.
+// (net_facts) and about the environment (net_switches), both read at every call: PK_NET_SENS_KC and PK_NET_THREADS are the live
+// switches of pk_env.hpp.
 using pk::NetFlavour; using pk::NetKernel; using pk::NetPlan;
-
-// dev knob PK_NET_SENS_KC: a column count below `cap`
-static int net_sens_kc(int cap) {
-  if (const char* e = getenv("PK_NET_SENS_KC")) { const int v = atoi(e); if (v >= 1 && v < cap) return v; }
-  return cap;
-}
 
 // Columns one workgroup of the sensitivity kernel carries on this network: the largest count whose LDS request (net_sens_lds_bytes; `score`:
 // net_sens_score_lds_bytes -- the rna baseline, its tangents and the accumulators come on top) stays within 160 KiB, at most n_var; 0 where
@@ -330,7 +326,7 @@ static int net_sens_kc(int cap) {
 static int net_sens_lds_columns(const pk_net* n, bool score) {
   if (n->d.S > 1024 || n->d.N > 512) return 0;
   const int fit = score ? pk::net_sens_score_max_columns(n->d, n->nnzT, pk::kNetLdsLimit) : pk::net_sens_max_columns(n->d, n->nnzT, pk::kNetLdsLimit);
-  return net_sens_kc(std::min(fit, n->d.n_var));
+  return pk::net_sens_kc(pk::env_live(), std::min(fit, n->d.n_var));
 }
 
 static pk::NetFacts net_facts(const pk_net* n) {
@@ -342,8 +338,8 @@ static pk::NetFacts net_facts(const pk_net* n) {
 }
 
 static pk::NetSwitches net_switches() {
-  const char* e = getenv("PK_NET_THREADS");
-  return {e ? atoi(e) : 0, net_sens_kc(16)};
+  const pk::Env e = pk::env_live();
+  return {e.net_threads, pk::net_sens_kc(e, 16)};
 }
 
 static pk_solver_opts net_opts(const pk_solver_opts* opts) {
@@ -496,13 +492,11 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       //   2 048 candidates UNIFORM IN THE OPTIMISER'S RAW BOUNDS (extreme rates, strong TF coupling):
       //     factor 0.5: 4 217 steps, median 0.21, p99 0.85, 0.7 % beyond the band;  0.25: 5 114 steps, median 0.11, p99 0.41, 0.5 % beyond;
       //     ROS34PW2: 7 478 steps, median 0.16, p99 0.31, 0.05 % beyond  (both methods: worst candidates 6-7 band widths off)
-      // (dev knob: PK_ARK_TOLFAC, read once)
-      static const double tolfac = [] { const char* v = getenv("PK_ARK_TOLFAC"); const double f = v ? atof(v) : 0.0; return (f > 0.0 && f <= 1.0) ? f : 0.25; }();
+      // (dev knob: PK_ARK_TOLFAC)
+      const pk::Env& env = pk::env();
       pk::NetSolveArgs aa = a;
-      aa.rtol *= tolfac; aa.atol *= tolfac;
-      static const double ctl_s = [] { const char* v = getenv("PK_ARK_SAFETY"); return v ? atof(v) : 0.0; }();      // dev knobs of the controller
-      static const double ctl_g = [] { const char* v = getenv("PK_ARK_GROW"); return v ? atof(v) : 0.0; }();
-      aa.ctl_safety = ctl_s; aa.ctl_grow = ctl_g;
+      aa.rtol *= env.ark_tolfac; aa.atol *= env.ark_tolfac;
+      aa.ctl_safety = env.ark_safety; aa.ctl_grow = env.ark_grow;      // dev knobs of the controller: PK_ARK_SAFETY, PK_ARK_GROW
       // [r3] arrow topologies: the dense two-lanes-per-protein layout, every stage vector in registers (PK_ARK_PAIR=0: round 2's kernel)
       const hipError_t ea = plan.kernel == NetKernel::ArkPair
                                 ? pk::launch_net_arkp(n->d, aa, n->nnzT, n->max_sites, (long long)B, stream)
