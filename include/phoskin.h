@@ -554,6 +554,48 @@ int pk_network_simulate_objective_grad_batch(pk_ctx*, pk_net*, pk_loss*, int64_t
  * accumulators on top (8 N + 32 bytes, and 8 N + 24 per column).  Pure host arithmetic. */
 int pk_network_objective_grad_columns_per_launch(pk_net*);
 
+/* Bounded Levenberg-Marquardt polish of B network candidates in lockstep over K chosen entries cols[k] of the candidate vector, every
+ * other entry held: the Gauss-Newton consumer of pk_network_simulate_objective_grad_batch's pred / dpred, with its state in HBM
+ * (csrc/pk_net_fit.hip; residual rows in csrc/pk_net_fit.hpp, row algebra in csrc/pk_lm.hpp).  Candidate b minimises
+ *   cost = 1/2 sum_m obj_w[m] F_m(x),  F = pk_network_simulate_objective_batch's F [3] for loss_mode 0 (the only loss this fit has: a robust
+ *   loss would need reweighting), obj_w [3] >= 0 the caller's scalarisation,
+ * as a least-squares problem with the rows sqrt(obj_w[m] norm_m lambda_m w_i) (pred_i - obs_i) for every observation i of modality m, in the
+ * caller's (protein | rna | phospho) list order, and sqrt((sum_m obj_w[m]) lambda_prior / (5 N)) (p_c - d_c) / (d_c + 1e-6) for every FITTED
+ * column c in A, B, C, D, E (defaults != NULL); the prior of the held entries is a constant of the fit.  With x_is_raw the fit runs on the
+ * raw entries: dpred is the raw derivative, the prior row's carries softplus'.  lb, ub bound the fitted entries in the space of x.
+ *   x0, x [B,n_var]; y0 [S] | [B,S]; defaults [n_var] | NULL; lb, ub [K] | [B,K], both NULL = no box; cost [B]; F [B,3]; JTJ [B,K,K] | NULL;
+ *   reason [B] | NULL; status [B] | NULL: DEVICE pointers.  t [T], cols [K], lambdas [4] = {protein, rna, phospho, prior}, obj_w [3],
+ *   counters [6] = {iterations, simulated candidates, launches, host waits, Jacobian phases, trial rounds}: HOST.
+ * The rules and constants are pk_fit_protein_rows_batch's (Marquardt scaling, mu0 = 1e-3, levels mu, 4 mu, 16 mu ... up to 12 per
+ * iteration, fit->trial_levels of them per launch, the first acceptable one taken, projection on the box, ftol / xtol); fit->log_space and
+ * fit->use_reg must be 0.  reason: 0 ftol / xtol, 1 gradient / empty free set, 2 damping budget, 3 max_iter, 4 the Jacobian launch flagged
+ * the candidate (any chunk): the row stops at its last accepted point and never steps from NaN.
+ * One iteration is a Jacobian phase -- gather, ONE tangent launch on the active rows (pk_network_simulate_objective_grad_batch with its
+ * route rules: LDS where columns fit, HBM slabs elsewhere or with PK_KERNEL_HBM, chunks of KC columns), the normal-equations kernel; in row
+ * chunks where dpred would pass 1 GiB -- and trial rounds: the trials kernel, ONE plain order-3 fused-objective launch on (levels x pending
+ * rows) trial candidates (that entry point with no columns), the accept kernel.  The host waits once per phase and once per round, for one
+ * flag per row.  State and scratch live in the grow-only fit arena of the context (no allocation per iteration); the call holds the
+ * context's lock and returns after its last wait.
+ * Cost consistency: a tangent launch controls its steps on state and tangents together, so its trajectory lies within rtol / atol of the
+ * plain launch's, not on it.  Every cost the gain ratio compares comes from PLAIN launches: the start cost from one at clip(x0), every
+ * trial's from its round's, and an accepted trial's cost and F become the row's own.  The Jacobian phase contributes A = J^T J and
+ * g = J^T r only, r from its own pred.  Hence F equals pk_network_simulate_objective_batch at the returned x BIT FOR BIT (same opts with
+ * PK_METHOD_ROS34PW2 / PK_LINSOLVE_STRUCTURED; PK_KERNEL_HBM: PK_KERNEL_WORKSPACE), and cost = 1/2 ((obj_w0 F0 + obj_w1 F1) + obj_w2 F2).
+ * Failures: a flagged trial has F = fail_value and is never acceptable; a flagged Jacobian launch is reason 4.  status is the row's last
+ * Jacobian launch OR-ed with the trial launches looked at in the iteration that followed (max_iter = 0: the start launch).
+ * JTJ belongs to the point of the row's last Jacobian phase (one accepted step behind x unless the last iteration took none); a row
+ * whose only Jacobian launch was flagged leaves its JTJ unwritten.  max_iter = 0: x = clip(x0), its cost and F, reason 3, JTJ NOT WRITTEN,
+ * counters = {0, B, 3, 0, 0, 0}.  Every sum is one thread's sequential sum in list order, prior rows last (no atomics): a row's x, cost,
+ * F and JTJ do not depend on the rows around it, their order, or trial_levels.
+ * PK_ERR_ARG: K < 1 or > n_var, a repeated or out-of-range column, a null required pointer, one of lb / ub alone, a negative obj_w,
+ * log_space / use_reg, trial_levels outside 0..12, max_iter < 0, T other than the loss handle's.  PK_ERR_UNSUPPORTED wherever the two
+ * launches answer it, and for a K whose damped system (K (K + 1) / 2 + 9 K doubles) passes 160 KiB of LDS.  B = 0 is PK_OK. */
+int pk_network_fit_batch(pk_ctx*, pk_net*, pk_loss*, int64_t B, const double* x0, int x_is_raw, const double* y0, int y0_is_batched,
+                         const double* t_host, int T, const pk_solver_opts* opts, const int32_t* cols_host, int K, const double* defaults,
+                         const double* lambdas, const double* obj_w, const double* lb, const double* ub, int bounds_are_batched,
+                         const pk_fit_opts* fit, double fail_value, double* x, double* cost, double* F, double* JTJ, int32_t* reason,
+                         int32_t* status, int64_t counters[6]);
+
 /* Timing hook for bench.py: runs `iters` back-to-back launches of pk_solve_protein_batch on the context's
  * stream between two hipEvents and returns the mean kernel time per launch in milliseconds (< 0 on error). */
 double pk_time_solve_protein_batch(pk_ctx*, int iters, int model, int n_sites, int64_t B,

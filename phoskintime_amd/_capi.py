@@ -78,7 +78,7 @@ SYMBOLS = (
     "pk_network_loss_create", "pk_network_loss_destroy", "pk_network_objective_batch", "pk_network_simulate_objective_batch", "pk_network_observables_batch", "pk_network_simulate_measure_batch", "pk_frechet_batch", "pk_loss_fn_batch_host", "pk_network_resolve_method",
     "pk_network_workspace_bytes", "pk_network_simulate_sens_batch", "pk_network_sens_columns_per_launch",
     "pk_network_simulate_objective_grad_batch", "pk_network_objective_grad_columns_per_launch",
-    "pk_network_sens_hbm_columns", "pk_network_sens_workspace_bytes",
+    "pk_network_sens_hbm_columns", "pk_network_sens_workspace_bytes", "pk_network_fit_batch",
     "pk_comm_unique_id", "pk_comm_init", "pk_comm_rank", "pk_comm_world", "pk_allgather_f64", "pk_comm_destroy",
 )
 
@@ -173,6 +173,9 @@ def load():
     lib.pk_network_objective_grad_columns_per_launch.restype = i32; lib.pk_network_objective_grad_columns_per_launch.argtypes = [vp]
     lib.pk_network_sens_hbm_columns.restype = i32; lib.pk_network_sens_hbm_columns.argtypes = [vp, i32, i32]
     lib.pk_network_sens_workspace_bytes.restype = i64; lib.pk_network_sens_workspace_bytes.argtypes = [vp, vp, i64, i32, i32]
+    lib.pk_network_fit_batch.restype = i32
+    lib.pk_network_fit_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, optp, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(FitOpts), dbl,
+                                         vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int64 * 6)]
     lib.pk_network_resolve_method.restype = i32; lib.pk_network_resolve_method.argtypes = [vp, optp]
     lib.pk_network_workspace_bytes.restype = i64; lib.pk_network_workspace_bytes.argtypes = [vp, vp, i64]
     lib.pk_loss_fn_batch_host.restype = i32

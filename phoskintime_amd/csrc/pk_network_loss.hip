@@ -322,6 +322,17 @@ int pk_loss_fused_tables(const pk_loss* l, const double** obs, const double** w,
   return 1;
 }
 
+// for the fit driver (pk_net_fit.hip): the observations and weights in the caller's (protein | rna | phospho) list order, the counts, the
+// normalisations and the grid length
+int pk_loss_fit_view(const pk_loss* l, int32_t* n, const double** obs, const double** w, double* norms, int* T) {
+  if (!l) return 0;
+  n[0] = l->d.n_prot; n[1] = l->d.n_rna; n[2] = l->d.n_pho;
+  obs[0] = l->d.obs_prot; obs[1] = l->d.obs_rna; obs[2] = l->d.obs_pho;
+  w[0] = l->d.w_prot; w[1] = l->d.w_rna; w[2] = l->d.w_pho;
+  norms[0] = l->d.norm_p; norms[1] = l->d.norm_r; norms[2] = l->d.norm_ph; *T = l->T;
+  return 1;
+}
+
 void pk_network_loss_destroy(pk_loss* l) {
   if (!l) return;
   for (void* p : l->allocs) (void)hipFree(p);

@@ -457,6 +457,77 @@ class NetworkEngine:
         out["status"]._keepalive = (xd, yd, dd, ch)  # type: ignore[attr-defined]
         return out
 
+    def fit_batch(self, loss, x0, t_eval, cols, lb=None, ub=None, obj_w=(1.0, 1.0, 1.0), defaults=None, lambdas=(1.0, 1.0, 1.0, 0.0), y0=None,
+                  raw: bool = False, max_iter: int = 50, trial_levels: int = 0, ftol: float = 1e-10, xtol: float = 1e-10, rtol: Optional[float] = None,
+                  atol: Optional[float] = None, max_steps: int = 1000000, err_norm: str = "max", fail_value: float = 1e12, loss_mode: int = 0,
+                  want_JTJ: bool = True, want_reason: bool = True, want_status: bool = True, method: str = "auto", kernel: str = "auto"):
+        """Bounded Levenberg-Marquardt polish of the B candidates ``x0`` over the entries ``cols`` of the candidate vector, every other entry
+        held, wholly on the device (``pk_network_fit_batch``): candidate b minimises ``cost = 1/2 sum_m obj_w[m] F_m`` with ``F`` the
+        three objectives of ``simulate_objective_batch`` for ``loss_mode = 0`` inside the box ``lb <= x[cols] <= ub`` ([K] or [B, K], in the
+        space of ``x0``: raw entries with ``raw=True``; both None = no box).  Returns ``(x [B, n_var], cost [B], F [B, 3], JTJ [B, K, K] or
+        None, reason [B] or None, status [B] or None, counters)`` -- GPU tensors and a dict of the six counters.  ``reason``: 0 ftol / xtol,
+        1 gradient / empty free set, 2 damping budget, 3 ``max_iter``, 4 the Jacobian launch flagged the candidate.  ``F`` is bit-equal to
+        ``simulate_objective_batch(method="rosw", kernel="lds")`` (``kernel="hbm"`` here: ``kernel="workspace"`` there) at the returned
+        ``x`` with the same tolerances: every cost the fit compares comes from such plain launches, the tangent launch of an iteration gives
+        the step only.  ``JTJ`` is J^T J of the scaled residuals at each row's last Jacobian phase (``polish.covariance``).  One iteration
+        costs one ``simulate_objective_grad_batch`` launch on the active rows and one plain launch per trial round; tolerances default to the
+        order-3 kernel's 1e-7 / 1e-9; ``kernel`` "auto" or "hbm" as there."""
+        if method not in ("auto", "rosw"):
+            raise ValueError("method must be 'auto' or 'rosw': the fit integrates with the order-3 method")
+        if kernel not in ("auto", "lds", "hbm"):
+            raise ValueError("kernel must be 'auto', 'lds' or 'hbm'")
+        if int(loss_mode) != 0:
+            raise ValueError("fit_batch minimises the squared loss (loss_mode 0) only: a robust loss would need reweighted rows")
+        if loss not in self._n_obs:
+            raise ValueError("loss must be a handle made by this engine's make_loss (and not freed)")
+        rtol = 1e-7 if rtol is None else rtol
+        atol = 1e-9 if atol is None else atol
+        dev = torch.device("cuda", self.ctx.device)
+        xd = _dev_f64(x0, dev)
+        if xd.dim() == 1:
+            xd = xd.unsqueeze(0)
+        if xd.shape[1] != self.n_var:
+            raise ValueError(f"x0 must be [B, {self.n_var}]")
+        B = xd.shape[0]
+        yd = _dev_f64(self.default_y0() if y0 is None else y0, dev)
+        if yd.shape == (self.S,):
+            yb = 0
+        elif yd.shape == (B, self.S):
+            yb = 1
+        else:
+            raise ValueError(f"y0 must be [{self.S}] or [{B}, {self.S}]")
+        th = np.ascontiguousarray(np.atleast_1d(np.asarray(t_eval, dtype=np.float64)))
+        T = th.size
+        ch = _i32(np.atleast_1d(cols)).reshape(-1)
+        K = int(ch.size)
+        if (lb is None) != (ub is None):
+            raise ValueError("lb and ub: give both or neither")
+        lbd = ubd = None
+        bb = 0
+        if lb is not None:
+            lbd, ubd = _dev_f64(lb, dev), _dev_f64(ub, dev)
+            if lbd.shape != ubd.shape or lbd.shape not in ((K,), (B, K)):
+                raise ValueError(f"lb and ub must both be [{K}] or [{B}, {K}]")
+            bb = int(lbd.dim() == 2)
+        dd = _dev_f64(defaults, dev) if defaults is not None else None
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        x, cost, F = new(B, self.n_var), new(B), new(B, 3)
+        JTJ = torch.zeros((B, K, K), dtype=torch.float64, device=dev) if want_JTJ else None
+        reason = torch.zeros((B,), dtype=torch.int32, device=dev) if want_reason else None
+        status = torch.zeros((B,), dtype=torch.int32, device=dev) if want_status else None
+        lam = (C.c_double * 4)(*[float(v) for v in lambdas])
+        ow = (C.c_double * 3)(*[float(v) for v in obj_w])
+        counters = (C.c_int64 * 6)()
+        opts = self._opts(method, kernel, rtol=rtol, atol=atol, max_steps=max_steps, err_norm=err_norm)
+        fo = _capi.default_fit_opts(max_iter=int(max_iter), trial_levels=int(trial_levels), ftol=float(ftol), xtol=float(xtol))
+        self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        self.ctx.check(self.ctx.lib.pk_network_fit_batch(
+            self.ctx.handle, self._h, loss, B, _ptr(xd), int(raw), _ptr(yd), yb, th.ctypes.data, T, C.byref(opts), ch.ctypes.data if K else None, K,
+            _ptr(dd), C.cast(lam, C.c_void_p), C.cast(ow, C.c_void_p), _ptr(lbd), _ptr(ubd), bb, C.byref(fo), float(fail_value), _ptr(x), _ptr(cost),
+            _ptr(F), _ptr(JTJ), _ptr(reason), _ptr(status), C.byref(counters)))
+        names = ("iterations", "simulated", "launches", "host_waits", "jacobian_phases", "trial_rounds")
+        return x, cost, F, JTJ, reason, status, dict(zip(names, (int(v) for v in counters)))
+
     def resolved_method(self, method: str = "auto", kernel: str = "auto") -> str:
         """The integrator ``simulate_batch(method=, kernel=)`` will run on this network -- "ark", "rosw" or "dp5" -- as decided by the
         library itself (``pk_network_resolve_method``: network size, sites per protein AND the LDS footprint of the order-4 kernel).

@@ -27,6 +27,7 @@ class GlobalODEBatch:
         self.eng = eng
         self.time_grid = np.asarray(time_grid, dtype=np.float64)
         self.loss = eng.make_loss(loss_data, self.time_grid.size)
+        self.loss_data = loss_data         # the host twin of ``polish`` forms its residual scales from it
         self.defaults = eng.pack_params(*(defaults[k] for k in ("c_k", "A_i", "B_i", "C_i", "D_i", "Dp_i", "E_i", "tf_scale")))
         self.lam = (float(lambdas["protein"]), float(lambdas["rna"]), float(lambdas["phospho"]), float(lambdas["prior"]))
         self.fail_value = float(fail_value)
@@ -82,6 +83,23 @@ class GlobalODEBatch:
             from .. import _capi
             raise _capi.PhoskinError("evaluate_with_grad: " + (self.eng.ctx.lib.pk_last_error(self.eng.ctx.handle) or b"").decode())
         return out["F"], out["dF"]
+
+    def polish(self, X, cols, obj_w=(1.0, 1.0, 1.0), max_iter: int = 50, driver: str = "native", **kw):
+        """Drive every candidate of X [b, n_var] (raw) to the nearest local minimum of ``1/2 sum_m obj_w[m] F_m`` over its raw entries
+        ``cols``, every other entry held, inside the problem's bounds ``xl / xu`` where it has them: ``polish.polish_batch`` with the
+        problem's own loss handle, defaults, lambdas, tolerances and y0.  Returns its ``PolishResult``; ``F`` there is bit-equal to the
+        order-3 fused objective at the returned ``x``.  The squared loss only (``loss_mode`` 0)."""
+        from . import polish as _polish
+        if self.loss_mode != 0:
+            raise ValueError("polish minimises the squared loss (loss_mode 0) only")
+        cols = np.asarray(np.atleast_1d(cols), dtype=np.int64).reshape(-1)
+        lb = ub = None
+        if self.xl is not None and self.xu is not None:
+            lb = np.broadcast_to(np.asarray(self.xl, float), (self.n_var,))[cols].copy()
+            ub = np.broadcast_to(np.asarray(self.xu, float), (self.n_var,))[cols].copy()
+        return _polish.polish_batch(self.eng, self.loss, self.loss_data, X, self.time_grid, cols, lb=lb, ub=ub, obj_w=obj_w, defaults=self.defaults,
+                                    lambdas=self.lam, y0=self.y0, raw=True, max_iter=max_iter, driver=driver, rtol=self.rtol, atol=self.atol,
+                                    max_steps=self.max_steps * self.time_grid.size, err_norm=self.err_norm, fail_value=self.fail_value, **kw)
 
     def evaluate(self, X) -> np.ndarray:
         """X [B, n_var] raw -> F [B, 3] (host).  Under an initialised ``torch.distributed`` group the candidates are dealt round-robin over
