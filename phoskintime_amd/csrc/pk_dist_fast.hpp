@@ -25,6 +25,11 @@
 //   * LRP8 and LRP12 take their error estimate as a repeated difference: two solves, then NS - 2 stages v <- v - M^{-1} v, each cheaper than a
 //     solve (one multiply and one FMA per row, the group sum's input from a sum carried from stage to stage); y_new is summed in that basis
 //     (ResolventTab::BN) and the estimate is the last v times E_2 / gamma -- no second accumulation.  RODAS4 keeps both weighted sums;
+//   * SCALED rows (dist_scaled(), below: the parked LRP12 layouts with registers to spare, the benchmark's 4 x 8 resident among them): a site
+//     row goes through the stages in units of its own coupling weight c_j = winv_j s_j (s_j: the row's rate, fixed per replica in the
+//     prologue), so that x_P enters every row with the coefficient 1: a solve and a difference stage are ONE FMA per row, the group sum's
+//     input is an FMA dot product, and nothing is tracked from stage to stage.  The state is divided into those units once per step
+//     (rho_j = y_j ic_j) and y_new and the error row are multiplied back once per step.  Described at factor() in the kernel;
 //   * no LDS-pipe instruction in the solve chain; LDS only as thread-private parking space in the PARK layouts (below).
 //
 // pk_dist_rows.hpp holds the rows a lane carries (Stg) and what is done for every row of a lane -- the vector updates, both error norms,
@@ -192,6 +197,24 @@ template <> struct DistWaveTrace<0> {      // the shipped kernels: nothing
   __device__ __forceinline__ void exit() const {}
 };
 
+// Which layouts carry their site rows in units of the rows' coupling weight (the scaled stages of factor() / solve() / diff() in the kernel): a
+// trait of the method, the rows per lane and the row placement, shared by the four output classes of a layout as they share its placement.
+// Scaling keeps 1 / s_j of every scaled row in registers (the parked slots have no room for it at the occupancy they run at), two VGPRs per
+// row that nothing can take back, so it is on exactly where no specialised kernel of the layout loses a wave per SIMD to them
+// (tools/kernel_resources.py against the waves the layout's parked slots admit; the table is in DESIGN.md 4.3):
+//   resident   6 and 8 rows per lane (n = 21, 22, 29, 30 on four lanes, 41 .. 46 and 57 .. 62 on eight; the benchmark's 4 x 8, its 256-thread
+//              variant and the traced build among them);
+//   shadowed   5, 6 and 7 rows per lane (n = 19, 20, 23, 24, 27, 28 on four lanes, 39, 40, 47, 48, 55, 56 on eight; and the resident sizes of
+//              those row counts under PK_DIST_LAYOUT=shadow).
+// Five resident rows run at five waves per SIMD with 96 registers and none to spare (104 scaled); at seven resident rows the sol + sum kernel
+// would need 130 against the 128 of four waves; at eight shadowed rows the flat-output kernel of the four-lane layout 171 against the 168
+// of three; the unparked layouts (RPL <= 4, LRP12 and the RODAS4 / LRP8 table) were not tried: all of these keep plain units.
+// PK_DIST_SCALE_MIN: the smallest rate that serves as a row's scale (the kernel's prologue).
+template <int METHOD, int RPL, bool PARK, bool RES> constexpr bool dist_scaled() {
+  return PARK && ResolventTab<METHOD>::DIFFERENCE && (RES ? (RPL == 6 || RPL == 8) : (RPL >= 5 && RPL <= 7));
+}
+constexpr double PK_DIST_SCALE_MIN = 0x1p-600;
+
 // NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
 //
 // RES = true is the RESIDENT layout, for sizes whose whole state fits the lane layout (G * RPL >= n + 2): the state vector is laid over
@@ -209,6 +232,9 @@ template <int G, int RPL, int METHOD, bool PARK = false, int MINB = (PARK ? 2 : 
 __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) {
   using Tab = ResolventTab<METHOD>;
   using Vec = Stg<RPL, RES>;
+  constexpr bool SCL = dist_scaled<METHOD, RPL, PARK, RES>();     // scaled site rows (factor(), below); J0: the first of them
+  constexpr int J0 = RES ? 1 : 0;
+  static_assert(!SCL || RPL - J0 >= 2, "the scaled rows' dot product runs on two chains");
   static_assert(!TRACE || NT == 64, "the trace holds one record per workgroup: one wave each");
   DistWaveTrace<TRACE> trace;
   trace.enter();
@@ -310,8 +336,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       }
     }
     // An idle row (i >= n: rate 0, initial value 0) holds +0 or -0 in every accepted state -- each of its stage values is
-    // fma(0, x_P, +-0) with x_P finite -- so its clipped value is a zero already.  Adding a zero of either sign instead of +0.0 can
-    // change the row sum only from one zero to the other, and the running sum it is added to started from +0.0 and takes either zero
+    // fma(0, x_P, +-0) with x_P finite; a scaled row has scale 0 there and is fma(0, A_j, +0) -- so its clipped value is a zero already.
+    // Adding a zero of either sign instead of +0.0 can change the row sum only from one zero to the other, and the running sum it is added to started from +0.0 and takes either zero
     // to the same bits.  Only normalize (which would read y0 past its end) still needs the mask; the run-time kernel keeps it.
     const bool masked = CFG::LITERAL || CFG::normalize(A);
     double vs[RPL];
@@ -441,6 +467,22 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     const double d0 = norm.group_max(y, y, y), d1 = norm.group_max(f0, y, y);      // |y| / sc and |f0| / sc with sc = atol + rtol |y|
     h = step_h0(d0, d1, A.h0);
   }
+  // ---- scaled rows: the scale s_j of a row, decided here once per replica and never again (a replica's bits do not depend on its wave
+  // mates).  It is the rate S_j itself wherever |S_j| >= 2^-600 (a NaN or inf rate included: it reaches Scw and ends as PK_ST_NONFINITE).
+  // An idle row, and a real site with rate 0 that starts at 0, has s_j = 0: rho_j = 0, c_j = 0 and every value of the row is 0 w_j, exactly
+  // zero.  Any other rate below the floor is replaced by the floor: the row keeps its decay exactly and receives an inflow 2^-600 P, of
+  // order 1e-181, which no output can show.  The scale replaces the rate in the row's K_SR slot -- from here on only factor() reads it;
+  // Dsum, the right-hand side above and the emitted values have used S_j itself -- and 1 / s_j (0 where s_j is 0) stays in registers.
+  double is[RPL];
+  if constexpr (SCL) static_for<RPL>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    if constexpr (j >= J0) {
+      const double sr = pk.template get<K_SR + j>();
+      const double s = !(fabs(sr) < PK_DIST_SCALE_MIN) ? sr : (sr == 0.0 && y.s[j] == 0.0) ? 0.0 : PK_DIST_SCALE_MIN;
+      pk.template set<K_SR + j>(s);
+      is[j] = s != 0.0 ? 1.0 / s : 0.0;
+    }
+  });
 
   // Arrow factors of M = I - q J (q = gamma h) for the current step size.
   //   rows: (1 + q B) x_R = r_R ; (1 + q d_i) x_i - q S_i x_P = r_i ; (1 + q Dsum) x_P - q C x_R - q sum x_i = r_P
@@ -461,7 +503,21 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // subtraction would keep nine to three digits of it, where the product is good to two ulps.  It costs the same: q winv_j is shared with
   // cw_j = (q winv_j) S_j, one multiply more per row than cw alone instead of one add.  The R slot's d is B; the P slot takes omw = 1
   // (v' = v - x_P) with its other fixups; shadowed, omwR = (q winvR) B and row P subtracts x_P itself.
-  double winv[RPL], cw[RPL], omw[RPL], winvR, omwR, Cl, sinv, Scw, qq, qs, ws0;
+  //
+  // SCALED rows (SCL: dist_scaled(), the parked LRP12 layouts).  A site row is carried through the stages in units of its own coupling
+  // weight: with c_j = winv_j s_j (= cw_j / q, s_j the row's scale: its rate, see the prologue), a stage value is v_j = c_j w_j, and with
+  // xq = q x_P every row of a solve and of a difference stage is ONE FMA on w with no coefficient on xq:
+  //   solve       u_j = cw_j x_P + winv_j r_j   ->  upsilon_j = winv_j rho_j + xq           (r_j = c_j rho_j; written with omw_j: solve())
+  //   difference  v'_j = omw_j v_j - cw_j x_P   ->  w'_j = fma(omw_j, w_j, -xq)
+  // and the group sum's input sum winv_j v_j is the FMA dot product sum g_j w_j with g_j = winv_j c_j: no product p_j, no add tree, no
+  // tracked sum (lam, Cl and the lam - psum cancellation are gone).  The state enters the first solve as rho_j = y_j ic_j with
+  // ic_j = piv_j / s_j (c_j ic_j = 1 to a few ulps), and leaves the step once: y_new_j = fma(c_j, A_j, y_j) with A_j the weighted sum of
+  // the row's w, e_j = c_j w_last,j.  factor() keeps c_j in cw[j]; Scw is q sum c_j, the same number up to rounding, and still what the
+  // cold non-finite test reads.  Resident: rows 1 .. RPL - 1 are scaled; row 0 (R slot, P slot, two sites) keeps plain units and its explicit
+  // term r_0 ws0 in the group sum, but takes xq like the others: cw[0] is cw_0 / q = winv_0 S_0, and in the P slot lane 1's own 1 / q
+  // (its chain's result for the "pivot" q), so that fma(cw_0, xq, 0) is x_P; qs = q^2 sinv is then the sum's one multiplier.  Shadowed:
+  // every site row is scaled; the shadow rows keep x_R and x_P = (q (C x_R + St) + r_P) sinv as they are, and xq = q x_P is one multiply.
+  double winv[RPL], cw[RPL], omw[RPL], g[RPL], ic[RPL], winvR, omwR, Cl, sinv, Scw, qq, qs, ws0;
   auto factor = [&](const double q) {
     qq = q;
     constexpr int X = RES ? 0 : 1;
@@ -492,14 +548,27 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     }
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      if constexpr (Tab::DIFFERENCE) {
+      if constexpr (SCL) {
+        // cw[j] is c_j = cw_j / q in every row (the K_SR slot of a scaled row holds its scale s_j)
+        // a scaled row's winv_j ends here: its solves are written with omw_j = 1 - winv_j (solve(), below)
+        cw[j] = winv[j] * pk.template get<K_SR + j>();
+        omw[j] = (q * winv[j]) * pk.template get<K_DG + j>();
+        if constexpr (j >= J0) {
+          g[j] = winv[j] * cw[j];
+          ic[j] = piv[X + j] * is[j];
+        }
+      } else if constexpr (Tab::DIFFERENCE) {
         const double qw = q * winv[j];
         cw[j] = qw * pk.template get<K_SR + j>();
         omw[j] = qw * pk.template get<K_DG + j>();
       } else cw[j] = q * pk.template get<K_SR + j>() * winv[j];
     });
     if constexpr (!Tab::DIFFERENCE) Scw = gsum<G>(tree_sum(cw), lane);
-    else if constexpr (!RES) {
+    else if constexpr (SCL) {
+      // the P slot's cw[0] is (1 / q) 0 here, before its fixup below
+      if constexpr (!RES) omwR = q * winvR * cB;
+      Scw = q * gsum<G>(tree_sum(cw), lane);
+    } else if constexpr (!RES) {
       omwR = q * winvR * cB;
       Cl = tree_sum(cw);
       Scw = gsum<G>(Cl, lane);
@@ -516,18 +585,58 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     sinv = fast_rcp(__builtin_fma(q, Dsum - Scw, 1.0));
     if constexpr (RES) {
       qs = q * sinv;
+      if constexpr (SCL) qs *= q;
       ws0 = winv[0] * w0;
+      if constexpr (SCL) cw[0] = isP ? winv[0] : cw[0]; else cw[0] = isP ? 1.0 : cw[0];
       winv[0] = isP ? 0.0 : winv[0];
-      cw[0] = isP ? 1.0 : cw[0];
       if constexpr (Tab::DIFFERENCE) omw[0] = isP ? 1.0 : omw[0];
     }
   };
   // u = M^{-1} r: ONE group reduction.  lam (difference stages): the sum of u over the lane's tracked rows, from the sum of t the solve
   // forms anyway: sum_j u_j = x_P Cl + sum_j t_j
   double lam = 0.0;
-  auto solve = [&](const Vec& r) {
+  // Scaled rows: the lane's input to the group sum, sum g_j w_j over its scaled rows as two FMA chains (resident: the first one starts from
+  // row 0's explicit term), and xq = q x_P from it.  Shadowed, the shadow rows' x_R and x_P come back through the arguments
+  auto gdot = [&](const Vec& v) {
+    if constexpr (SCL) {
+      constexpr int H = (RPL + J0) / 2;             // rows [0, H) on the first chain (resident: row 0 by its explicit term), [H, RPL) on the second
+      double a, b = g[H] * v.s[H];
+      if constexpr (RES) a = v.s[0] * ws0; else a = g[0] * v.s[0];
+#pragma unroll
+      for (int j = 1; j < H; ++j) a = __builtin_fma(g[j], v.s[j], a);
+#pragma unroll
+      for (int j = H + 1; j < RPL; ++j) b = __builtin_fma(g[j], v.s[j], b);
+      return a + b;
+    } else return 0.0;
+  };
+  auto xq_of = [&](const Vec& v, double& xR, double& xP) {
+    if constexpr (RES) return gsum<G>(gdot(v), lane) * qs;
+    else {
+      xR = v.R() * winvR;
+      xP = __builtin_fma(qq, __builtin_fma(cC, xR, gsum<G>(gdot(v), lane)), v.P()) * sinv;
+      return qq * xP;
+    }
+  };
+  // first (std::true_type: the first stage of a step, scaled rows only): the scaled rows come back as upsilon_j - rho_j, the stage itself
+  auto solve = [&](const Vec& r, auto first) {
     Vec u;
     double xR = 0.0;
+    if constexpr (SCL) {
+      // r and u: scaled rows in units of c_j (rho, upsilon), row 0 of the resident layout and the shadow rows in plain units.  A scaled
+      // row is written with omw_j, upsilon_j = rho_j - omw_j rho_j + xq, so that winv_j need not outlive factor() and the first stage
+      // upsilon_j - rho_j = fma(-omw_j, rho_j, xq) is formed without its cancellation (one operation where the plain rows take two; the
+      // second solve pays it back with its add)
+      double xP = 0.0;
+      const double xq = xq_of(r, xR, xP);
+      if constexpr (RES) u.s[0] = __builtin_fma(cw[0], xq, r.s[0] * winv[0]);
+      else { u.R() = xR; u.P() = xP; }
+#pragma unroll
+      for (int j = J0; j < RPL; ++j) {
+        if constexpr (decltype(first)::value) u.s[j] = __builtin_fma(-omw[j], r.s[j], xq);
+        else u.s[j] = __builtin_fma(-omw[j], r.s[j], r.s[j] + xq);
+      }
+      return u;
+    }
     if constexpr (!RES) xR = r.R() * winvR;
     double t[RPL];
 #pragma unroll
@@ -563,7 +672,17 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // the lanes; and the group sum that feeds x_P needs sum winv_j v_j = lam - sum omw_j v_j with lam = sum v_j carried from stage to stage
   // by one FMA, lam' = sum p_j - x_P Cl (p_j = omw_j v_j), instead of a second tree.  Resident: row 0 keeps its explicit term v_0 ws0 as
   // in solve(), and lam, the tree and Cl run over rows 1 .. RPL - 1 (none of them at one row per lane).
+  // Scaled rows: w'_j = fma(omw_j, w_j, -xq), one FMA per row after the dot product; row 0 of the resident layout and the shadow rows as above.
   auto diff = [&](Vec& v) {
+    if constexpr (SCL) {
+      double xR = 0.0, xP = 0.0;
+      const double xq = xq_of(v, xR, xP);
+      if constexpr (RES) v.s[0] = __builtin_fma(-cw[0], xq, omw[0] * v.s[0]);
+      else { v.R() *= omwR; v.P() -= xP; }
+#pragma unroll
+      for (int j = J0; j < RPL; ++j) v.s[j] = __builtin_fma(omw[j], v.s[j], -xq);
+      return;
+    }
     double p[RPL];
 #pragma unroll
     for (int j = 0; j < RPL; ++j) p[j] = omw[j] * v.s[j];
@@ -661,19 +780,46 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         // y + q b: q A joins row R (resident: k3 is A in lane 0 and 0 elsewhere, so the FMA is uniform over the lanes)
         Vec r = y;
         if constexpr (RES) r.s[0] = __builtin_fma(qq, k3, y.s[0]); else r.R() = __builtin_fma(qq, cA, y.R());
-        z = solve(r);
-        trk_axpy(z, -1.0, y);
+        if constexpr (SCL) {
+          // the scaled rows enter as rho_j = y_j / c_j, and solve() hands back the first stage upsilon_j - rho_j in the same units
+#pragma unroll
+          for (int j = J0; j < RPL; ++j) r.s[j] = y.s[j] * ic[j];
+          z = solve(r, std::true_type{});
+#pragma unroll
+          for (int j = 0; j < Vec::NR; ++j) if (j < J0 || j >= RPL) z.s[j] -= y.s[j];
+        } else {
+          z = solve(r, std::false_type{});
+          trk_axpy(z, -1.0, y);
+        }
       }
-      Vec yn = y; trk_axpy(yn, Tab::B[0] / Tab::GAM, z);
+      // scaled rows: yn_j holds A_j, the weighted sum of the row's stage values in units of c_j, until the end of the step
+      Vec yn = y;
+      if constexpr (SCL) {
+#pragma unroll
+        for (int j = J0; j < RPL; ++j) yn.s[j] = 0.0;
+      }
+      trk_axpy(yn, Tab::B[0] / Tab::GAM, z);
       double err;
       if constexpr (Tab::DIFFERENCE) {
-        z = solve(z);
+        z = solve(z, std::false_type{});
         trk_axpy(yn, Tab::BN[0] / Tab::GAM, z);
         static_for<Tab::NS - 2>([&](auto mc) {
           constexpr int m = 1 + decltype(mc)::value;
           diff(z);
           trk_axpy(yn, Tab::BN[m] / Tab::GAM, z);
         });
+        if constexpr (SCL) {
+          // back to plain units, once per step: the candidate and the error row.  The scaled rows of the state were last read when rho was
+          // formed; the final FMA and the norm take them from their slots again (as state_bad() does) rather than keep them in registers
+          // through every stage
+          pk.fence();
+          static_for<RPL - J0>([&](auto jc) { constexpr int j = J0 + decltype(jc)::value; y.s[j] = pk.template get<K_Y + j>(); });
+#pragma unroll
+          for (int j = J0; j < RPL; ++j) {
+            yn.s[j] = __builtin_fma(cw[j], yn.s[j], y.s[j]);
+            z.s[j] *= cw[j];
+          }
+        }
         constexpr double e1 = (Tab::E[1] < 0.0 ? -Tab::E[1] : Tab::E[1]) / Tab::GAM;
         if constexpr (CFG::LITERAL) err = e1 * norm.group_max(z, y, yn); else err = e1 * norm.err_norm(z, y, yn);
       } else {
@@ -681,7 +827,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         static_for<Tab::NS - 1>([&](auto kc) {
           constexpr int kk = 1 + decltype(kc)::value;
           constexpr double bk = Tab::B[kk] / Tab::GAM, ek = Tab::E[kk] / Tab::GAM;
-          z = solve(z);
+          z = solve(z, std::false_type{});
           trk_axpy(yn, bk, z);
           if constexpr (kk == 1) u6 = trk_scale(ek, z); else trk_axpy(u6, ek, z);
         });
