@@ -183,6 +183,23 @@ def test_randmod_from_seven_sites(shim):
     assert plan(shim, RAND, 9, 2, kernel=K_GROUP).launches == 2
 
 
+def test_explicit_linsolve_reaches_the_lane_group_kernels_at_every_size_and_switch(shim):
+    """What tests/test_gpu_group_matrix.py relies on: with linsolve DENSE or STRUCTURED, every model, method and form runs on the lane-group
+    kernel at every size up to 64 states, whatever the environment switches say, at the width that holds the states."""
+    sizes = [(DIST, n) for n in (1, 6, 7, 14, 15, 30, 31, 62)] + [(SUCC, n) for n in (1, 6, 7, 14, 15, 30, 31, 62)] + [(RAND, n) for n in (1, 2, 3, 4, 5)]
+    switches = (dict(), dict(tpr=1), dict(tpr=0), dict(parity56=1), dict(parity56=0), dict(level6=1), dict(exact=0), dict(exact=2), dict(sched=-1))
+    for model, n in sizes:
+        S = 2 + (n if model != RAND else 2 ** n - 1)
+        G = 8 if S <= 8 else 16 if S <= 16 else 32 if S <= 32 else 64
+        for linsolve in (DENSE, STRUCTURED):
+            for method, form in ((LRP12, 0), (LRP8, 0), (RODAS4, 0), (RODAS4, 1), (BDF2, 0), (RK4, 0)):
+                for sw in switches:
+                    for kern in (K_AUTO, K_TPR):
+                        p = plan(shim, model, n, 37, method=method, linsolve=linsolve, stage_form=form, kernel=kern, **sw)
+                        assert (p.kernel, p.code, p.G, p.launches) == ("Group", OK, G, -(-37 // (256 // G))), (model, n, linsolve, method, form, sw, kern)
+                        assert p.structured == (linsolve == STRUCTURED and model != RAND)
+
+
 def test_unknown_kernel_and_the_launch_limit(shim):
     for model, n in ((DIST, 4), (SUCC, 8), (RAND, 3), (RAND, 6), (RAND, 9), (DIST, 70)):
         for kern in (K_WORKSPACE, -1):
