@@ -38,10 +38,10 @@ __device__ constexpr double DI[5][5] = {
     {-0.25, 0, 0, 0, 0},
     {-0.084, -0.166, 0, 0, 0},
     {0.19348346118010076, -0.04621125528694374, -0.39727220589315704, 0, 0},
-    {0.2536756417084803, -0.23483923299747125, -0.24860482604014308, -0.020231582670865906, 0},
-    {-0.04350805551100497, -0.008742057842904185, 0.02681898345231962, 0.27673623478725706, -0.5013051048856676}};
-__device__ constexpr double B[6] = {0.15791629516167136, 0.0, 0.18675894052400077, 0.6805652953093346, -0.27524053099500667, 0.25};
-__device__ constexpr double EB[6] = {0.0032044943984591762, 0.0, -0.0024462511366794577, -0.02148007591958727, 0.043946868068572426, -0.02322503541076487};
+    {0.25367564170848026293, -0.23483923299747125, -0.24860482604014308, -0.020231582670865906, 0},
+    {-0.04350805551100497, -0.008742057842904185, 0.02681898345231962, 0.27673623478725706, -0.50130510488566754551}};
+__device__ constexpr double B[6] = {0.15791629516167136, 0.0, 0.18675894052400077, 0.6805652953093346, -0.27524053099500669833, 0.25};
+__device__ constexpr double EB[6] = {0.0032044943984591762, 0.0, -0.0024462511366794577, -0.02148007591958727, 0.043946868068572426, -0.023225035410764872521};
 }  // namespace ark436
 
 // LDS parking: thread-private accumulators, slot-major [slot][row][thread] (conflict-free; padding rows are stored like the others: they

@@ -22,6 +22,7 @@
 // Outputs (sol / flat / fused Morris metric / status / n_steps) have exactly the semantics of Emitter in pk_solve_kernel.hpp.
 #pragma once
 #include "pk_solve_kernel.hpp"
+#include "pk_network_solve_ark.hpp"
 
 namespace pk {
 
@@ -522,17 +523,10 @@ __global__ __launch_bounds__(256) void wide_rand_kernel(const SolveArgs A, doubl
   if constexpr (ARK) {
     // ---- ARK4(3)6L[2]SA as a linearly implicit additive method (see pk_network_solve_ark.hpp): implicit operator A~ = g I - P with
     // P = (D_g - F) D_g^-1 (D_g - K) the approximate factorisation the sweeps invert; stage solves P Y = g r; h A~ Y = Y / gamma - h (g r)
-    constexpr double AGAM = 0.25;
-    constexpr double AE[5][5] = {{0.5, 0, 0, 0, 0}, {0.221776, 0.110224, 0, 0, 0},
-                                 {-0.04884659515311858, -0.177720652326401, 0.8465672474795196, 0, 0},
-                                 {-0.15541685842491548, -0.3567050098221991, 1.0587258798684427, 0.30339598837867193, 0},
-                                 {0.20142435067267633, 0.008742057842904185, 0.15993995707168115, 0.4038290605220775, 0.22606457389066084}};
-    constexpr double DI[5][5] = {{-0.25, 0, 0, 0, 0}, {-0.084, -0.166, 0, 0, 0},
-                                 {0.19348346118010076, -0.04621125528694374, -0.39727220589315704, 0, 0},
-                                 {0.2536756417084803, -0.23483923299747125, -0.24860482604014308, -0.020231582670865906, 0},
-                                 {-0.04350805551100497, -0.008742057842904185, 0.02681898345231962, 0.27673623478725706, -0.5013051048856676}};
-    constexpr double BB[6] = {0.15791629516167136, 0.0, 0.18675894052400077, 0.6805652953093346, -0.27524053099500667, 0.25};
-    constexpr double EB[6] = {0.0032044943984591762, 0.0, -0.0024462511366794577, -0.02148007591958727, 0.043946868068572426, -0.02322503541076487};
+    // the table is ark436's, the one copy under csrc/ (tests/test_integrator_tables.py proves it against the rationals)
+    using ark436::AE; using ark436::DI; using ark436::EB;
+    constexpr double AGAM = ark436::GAM;
+    constexpr const double (&BB)[6] = ark436::B;
     double* Y = Ys;  double* w = U[0];  double* v = U[1];  double* gr = U[2];
     double* Rr[4] = {U[3], f, extra, extra + S};                        // R_3 .. R_6
     double* sb = extra + 2 * (size_t)S;  double* se = extra + 3 * (size_t)S;

@@ -6,6 +6,8 @@ arithmetic (mpmath) and compare with the literals parsed out of the HIP sources,
   * ROS34PW2 (Rang-Angermann)   : the 8 order-3 W-method conditions, stiff accuracy, R(inf) = 0   (tools/check_ros34pw2.py)
   * RODAS4 resolvent weights    : re-derived from the stage table                 (tools/rodas4_resolvent.py)
   * LRP8 weights                : order 7 / embedded order 6 conditions solved afresh, A-stability on the imaginary axis (tools/restricted_pade.py)
+  * ARK4(3)6L[2]SA (Kennedy-Carpenter) : the rationals of tools/check_ark436.py, every additive order condition to order 4 (embedded: 3),
+                                  stiff accuracy and L-stability of the implicit tableau, one copy of the table under csrc/
 """
 import importlib.util
 import re
@@ -35,6 +37,76 @@ def _literals(text, name):
     m = re.search(r"\b" + name + r"\s*=\s*([-+0-9.eE]+)", text)
     assert m, name
     return [mp.mpf(m.group(1))]
+
+
+def _literals_2d(text, name):
+    """Rows of `NAME[r][c] = {{a, b, ...}, {...}, ...};` in a source file (the one-dimensional reader stops at the first closing brace)."""
+    m = re.search(r"\b" + name + r"\s*\[\d+\]\s*\[\d+\]\s*=\s*\{((?:\s*\{[^{}]*\}\s*,?)+)\s*\}\s*;", text)
+    assert m, name
+    return [[mp.mpf(x.strip()) for x in row.split(",") if x.strip()] for row in re.findall(r"\{([^{}]*)\}", m.group(1))]
+
+
+def test_ark436_table_matches_source_and_order_conditions():
+    """ARK4(3)6L[2]SA as compiled into csrc/pk_network_solve_ark.hpp (AE, DI = a^I - a^E, B, EB = b - bhat, GAM) against the rationals of
+    tools/check_ark436.py; its additive order conditions (order 4, embedded order 3, every coupling between the two tableaus), stiff
+    accuracy and L-stability of the implicit tableau, re-run in mpmath; and one copy of the table under csrc/."""
+    mp.mp.dps = 50
+    chk = _load("check_ark436")
+    src = (CSRC / "pk_network_solve_ark.hpp").read_text()
+    ns = src[src.index("namespace ark436 {"):src.index("}  // namespace ark436")]
+    fr = lambda x: mp.mpf(x.numerator) / mp.mpf(x.denominator)
+    AI = [[fr(x) for x in r] for r in chk.AI]; AE = [[fr(x) for x in r] for r in chk.AE]
+    b = [fr(x) for x in chk.b]; bh = [fr(x) for x in chk.bh]; c = [fr(x) for x in chk.c]
+    close = lambda lit, exact, what: abs(lit - exact) <= mp.mpf("1e-16") * abs(exact) or pytest.fail("%s: %s against %s" % (what, lit, exact))
+    # ---- the literals
+    assert _literals(ns, "GAM")[0] == fr(chk.g) == mp.mpf(1) / 4
+    sAE, sDI, sB, sEB = _literals_2d(ns, "AE"), _literals_2d(ns, "DI"), _literals(ns, r"\bB"), _literals(ns, "EB")
+    assert [len(r) for r in sAE] == [5] * 5 and [len(r) for r in sDI] == [5] * 5 and len(sB) == 6 and len(sEB) == 6
+    for i in range(5):                                   # rows i = 2 .. 6 of the tableaus, columns 1 .. 5
+        for j in range(5):
+            if j > i:                                    # the arrays hold the strictly lower triangle
+                assert sAE[i][j] == 0 and sDI[i][j] == 0 and AE[i + 1][j] == 0
+                continue
+            close(sAE[i][j], AE[i + 1][j], "AE[%d][%d]" % (i, j))
+            close(sDI[i][j], AI[i + 1][j] - AE[i + 1][j], "DI[%d][%d]" % (i, j))
+    for j in range(6):
+        close(sB[j], b[j], "B[%d]" % j)
+        close(sEB[j], b[j] - bh[j], "EB[%d]" % j)
+    assert all(AE[i][5] == 0 for i in range(6)) and all(AI[i][i] == fr(chk.g) for i in range(1, 6))      # what the 5 x 5 arrays leave out: gamma on the diagonal
+    # ---- the conditions
+    mv = lambda A, v: [sum(A[i][j] * v[j] for j in range(6)) for i in range(6)]
+    dot = lambda u, v: sum(x * y for x, y in zip(u, v))
+    c2, c3 = [x * x for x in c], [x ** 3 for x in c]
+    tabs = (AI, AE)
+    tol = mp.mpf("1e-24")                                # the explicit entries are 13-digit rational approximations: residuals <= 3e-26
+
+    def residuals(w, order):
+        r = [dot(w, [1] * 6) - 1, dot(w, c) - mp.mpf(1) / 2, dot(w, c2) - mp.mpf(1) / 3] + [dot(w, mv(A, c)) - mp.mpf(1) / 6 for A in tabs]
+        if order == 4:
+            r += [dot(w, c3) - mp.mpf(1) / 4]
+            r += [dot(w, [ci * x for ci, x in zip(c, mv(A, c))]) - mp.mpf(1) / 8 for A in tabs] + [dot(w, mv(A, c2)) - mp.mpf(1) / 12 for A in tabs]
+            r += [dot(w, mv(A1, mv(A2, c))) - mp.mpf(1) / 24 for A1 in tabs for A2 in tabs]
+        return r
+
+    for A in tabs:
+        assert max(abs(sum(A[i]) - c[i]) for i in range(6)) < tol
+    assert len(residuals(b, 4)) == 14 and max(abs(v) for v in residuals(b, 4)) < tol
+    assert max(abs(v) for v in residuals(bh, 3)) < tol
+    assert max(abs(v) for v in residuals(bh, 4)[5:]) > mp.mpf("1e-4")                                   # embedded: order 3 only
+    # ---- implicit tableau: first stage explicit, stiffly accurate, L-stable
+    assert all(x == 0 for x in AI[0]) and AI[5] == b
+    R = lambda z: 1 + z * dot(b, list(mp.lu_solve(mp.eye(6) - z * mp.matrix(AI), mp.matrix([1] * 6))))
+    assert abs(R(mp.mpf("0.01")) - mp.e ** mp.mpf("0.01")) < mp.mpf("1e-10") and abs(R(mp.mpf("-1e15"))) < mp.mpf("1e-12")
+    assert all(abs(R(mp.mpc(0, y))) <= 1 + mp.mpf("1e-30") for y in (0.1, 1, 3, 10, 100, 1e4))
+    # ---- one copy: no other file of csrc/ spells an entry of the table out, and the pair kernels read this namespace
+    entries = set(re.findall(r"\d\.\d{10,}", ns))
+    assert len(entries) >= 30
+    for f in sorted(CSRC.glob("*.h*")):
+        text = f.read_text()
+        assert text.count("namespace ark436 {") == (1 if f.name == "pk_network_solve_ark.hpp" else 0), f.name
+        if f.name != "pk_network_solve_ark.hpp":
+            assert not [t for t in entries if t in text], f.name
+    assert "using namespace ark436;" in (CSRC / "pk_network_solve_arkp.hpp").read_text()
 
 
 def test_rodas4_table_satisfies_order_conditions_and_matches_source():

@@ -279,3 +279,51 @@ def test_threads_of_the_general_lds_kernel(shim):
         assert (tt(5, 5, net_threads=128), tt(6, 6, net_threads=64), tt(6, 6, net_threads=128)) == (128, 256, 256)
         assert (t(fl, K=4, S=128, N=64, **{cols: 4}), t(fl, K=5, S=128, N=64, **{cols: 5})) == (64, 256)      # 512 / 640
     assert t(PLAIN, K=40, sens_cols=40, **small) == 64 and t(LISTS, K=40, sens_cols=40, **small) == 64
+
+
+# The networks of tests/net_step_reference.py, on which tests/test_gpu_network_steps.py holds every integrator kernel to a one-step
+# restatement: (topology, N, S, max_sites) and the kernel of each of its routes -- default, method="rosw", method="rosw" + kernel="lds",
+# kernel="workspace", and the default with PK_ARK_PAIR=0 (no dense lane layout) -- with the threads of the general LDS kernel
+STEP_NETWORKS = {
+    "network_m0_small": ((0, 6, 20, 3), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "network_m1_small": ((1, 6, 21, 3), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "network_m2_small": ((2, 6, 32, 3), ("Ark", "CombReg", "Lds", "Workspace", "Ark"), 64),
+    "network_m4_small": ((4, 6, 20, 3), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m0_c4": ((0, 5, 21, 4), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m0_c6": ((0, 6, 29, 6), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m0_c8": ((0, 7, 38, 8), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m1_c4": ((1, 5, 21, 4), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m1_c6": ((1, 6, 29, 6), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m1_c8": ((1, 7, 38, 8), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m4_c4": ((4, 5, 21, 4), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m4_c6": ((4, 6, 29, 6), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m4_c8": ((4, 7, 38, 8), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 64),
+    "m2_c2": ((2, 6, 23, 2), ("Ark", "CombReg", "Lds", "Workspace", "Ark"), 64),
+    "m2_c3": ((2, 6, 33, 3), ("Ark", "CombReg", "Lds", "Workspace", "Ark"), 64),
+    "m2_c4": ((2, 5, 34, 4), ("Lds", "Lds", "Lds", "Workspace", "Lds"), 64),
+    "m0_wide": ((0, 70, 290, 4), ("ArkPair", "Reg", "Lds", "Workspace", "Ark"), 256),
+}
+
+
+def test_routes_of_the_step_reference_networks(shim):
+    import net_step_reference as nr
+    assert set(STEP_NETWORKS) == set(nr.GOLDEN_SMALL) | {s[0] for s in nr.SYNTHETIC}
+    for tag, (facts, kernels, lds_threads) in STEP_NETWORKS.items():
+        desc, net, X, y0, t = nr.case(tag)
+        model, N, S, max_sites = facts
+        assert (net.model, net.N, net.S, int(net.n_sites.max())) == facts, tag
+        # byte counts: an upper bound on each kernel's request (parameters, 8 vectors of S, 7 of N, the TF CSR twice over, the reductions,
+        # and the additive kernel's four parked block vectors per thread); every one is a fraction of its threshold
+        threads = -(-N // 64) * 64
+        lds = 8 * (X.shape[1] + 8 * S + 7 * N + net.n_K + net.total_sites + 2 * int(net.TF_indptr[-1]) + 32) + 8 * 4 * (2 + (1 << max_sites if model == 2 else max_sites)) * threads
+        assert lds <= 64 * KiB
+        kw = dict(model=model, N=N, S=S, n_var=X.shape[1], max_sites=max_sites, solve_lds=lds, reg_lds=lds, rk45_lds=lds, ark_lds=lds)
+        dense = model != 2                               # net_arkp_fits: a lane table (topologies 0 / 1 / 4, <= 8 sites) of <= 512 lanes
+        got = [plan(shim, arkp_fits=dense, **kw), plan(shim, arkp_fits=dense, **kw, **ROSW), plan(shim, arkp_fits=dense, **kw, **LDS),
+               plan(shim, arkp_fits=dense, kernel=K_WORKSPACE, **kw), plan(shim, arkp_fits=False, **kw)]
+        assert tuple(p.kernel for p in got) == kernels and all(p.code == OK for p in got), tag
+        additive = model != 2 or max_sites <= 3
+        assert [p.method for p in got] == [ARK436 if additive else ROS34PW2, ROS34PW2, ROS34PW2, ROS34PW2, ARK436 if additive else ROS34PW2], tag
+        assert got[2].threads == lds_threads and got[4].threads == -(-N // 64) * 64, tag
+        if not additive:
+            assert plan(shim, method=ARK436, **kw).msg == ARK_FITS
