@@ -29,7 +29,8 @@
 //     row goes through the stages in units of its own coupling weight c_j = winv_j s_j (s_j: the row's rate, fixed per replica in the
 //     prologue), so that x_P enters every row with the coefficient 1: a solve and a difference stage are ONE FMA per row, the group sum's
 //     input is an FMA dot product, and nothing is tracked from stage to stage.  The state is divided into those units once per step
-//     (rho_j = y_j ic_j) and y_new and the error row are multiplied back once per step.  Described at factor() in the kernel;
+//     (rho_j = y_j ic_j; or enters the first stage as itself, dist_stage1_state()) and y_new and the error row are multiplied back once
+//     per step.  Described at factor() and solve() in the kernel;
 //   * no LDS-pipe instruction in the solve chain; LDS only as thread-private parking space in the PARK layouts (below).
 //
 // pk_dist_rows.hpp holds the rows a lane carries (Stg) and what is done for every row of a lane -- the vector updates, both error norms,
@@ -214,6 +215,25 @@ template <int METHOD, int RPL, bool PARK, bool RES> constexpr bool dist_scaled()
   return PARK && ResolventTab<METHOD>::DIFFERENCE && (RES ? (RPL == 6 || RPL == 8) : (RPL >= 5 && RPL <= 7));
 }
 constexpr double PK_DIST_SCALE_MIN = 0x1p-600;
+// Which scaled layouts form the FIRST stage of a step from the state rows themselves (solve(r, std::true_type) in the kernel): t_j = kappa_j y_j
+// with kappa_j = d_j / s_j in the registers that otherwise hold 1 / s_j, instead of rho_j = y_j ic_j with ic_j = piv_j / s_j formed in
+// factor().  One operation fewer per scaled row and step, but winv_j of the scaled rows then lives from factor() to the first dot product,
+// and two layouts have no registers for that: the flat-output kernels of six resident rows stand at the 128 of four waves per SIMD and
+// would need 130 (4 x 6) and 132 (8 x 6); of five shadowed rows, 8 x 5 would need 132 against the same 128 and 4 x 5 stands at 128 exactly.
+// So: resident 8 rows, shadowed 6 and 7.  A trait of the layout, shared by its four output classes like dist_scaled(), since it moves bits
+// (by roundings: tools/stage1_form_sensitivity.py).
+template <int METHOD, int RPL, bool PARK, bool RES> constexpr bool dist_stage1_state() {
+  return dist_scaled<METHOD, RPL, PARK, RES>() && (RES ? RPL == 8 : RPL != 5);
+}
+// Which resident instantiations end factor() with arithmetic on two per-lane constants (selP, notP: two VGPR pairs) where the others keep
+// four selects on isP.  Same bits either way (factor(), below), so this is decided kernel by kernel: everywhere but where the four
+// registers cost a wave per SIMD -- 96 -> 102 VGPRs at five rows (sol + sum, sol only: five waves), 128 -> 136 in the flat-output kernel at
+// six rows (four waves), and two unparked kernels (one row run-time 78 -> 82, two rows flat-only 72 -> 76).  A parked slot instead of the
+// registers does not help the first: 16 slots x 512 B is what lets five waves per SIMD share the CU's LDS.
+template <int RPL, class CFG> constexpr bool dist_pslot_arith() {
+  constexpr bool any = std::is_same<CFG, DistAny>::value, flat = std::is_same<CFG, DistFlatOnly>::value;
+  return !(RPL == 1 && any) && !(RPL == 2 && flat) && !(RPL == 5 && !any && !flat) && !(RPL == 6 && flat);
+}
 
 // NT threads per workgroup (256, or 64 = one wave: a finished wave's slot is refilled at once instead of when the slowest of four is done)
 //
@@ -234,7 +254,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   using Vec = Stg<RPL, RES>;
   constexpr bool SCL = dist_scaled<METHOD, RPL, PARK, RES>();     // scaled site rows (factor(), below); J0: the first of them
   constexpr int J0 = RES ? 1 : 0;
-  static_assert(!SCL || RPL - J0 >= 2, "the scaled rows' dot product runs on two chains");
+  constexpr bool S1 = dist_stage1_state<METHOD, RPL, PARK, RES>();     // the first stage from the state rows (solve(), below)
+  constexpr bool PAR = RES && dist_pslot_arith<RPL, CFG>();        // the P slot's fix-ups as arithmetic (factor(), below)
   static_assert(!TRACE || NT == 64, "the trace holds one record per workgroup: one wave each");
   DistWaveTrace<TRACE> trace;
   trace.enter();
@@ -472,7 +493,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // An idle row, and a real site with rate 0 that starts at 0, has s_j = 0: rho_j = 0, c_j = 0 and every value of the row is 0 w_j, exactly
   // zero.  Any other rate below the floor is replaced by the floor: the row keeps its decay exactly and receives an inflow 2^-600 P, of
   // order 1e-181, which no output can show.  The scale replaces the rate in the row's K_SR slot -- from here on only factor() reads it;
-  // Dsum, the right-hand side above and the emitted values have used S_j itself -- and 1 / s_j (0 where s_j is 0) stays in registers.
+  // Dsum, the right-hand side above and the emitted values have used S_j itself -- and 1 / s_j (0 where s_j is 0) stays in registers, as
+  // kappa_j = d_j / s_j where the first stage is formed from the state rows (S1: dist_stage1_state()).
   double is[RPL];
   if constexpr (SCL) static_for<RPL>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
@@ -481,8 +503,16 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       const double s = !(fabs(sr) < PK_DIST_SCALE_MIN) ? sr : (sr == 0.0 && y.s[j] == 0.0) ? 0.0 : PK_DIST_SCALE_MIN;
       pk.template set<K_SR + j>(s);
       is[j] = s != 0.0 ? 1.0 / s : 0.0;
+      if constexpr (S1) is[j] *= pk.template get<K_DG + j>();
     }
   });
+  // ---- the P slot's two constants (PAR: dist_pslot_arith()): selP is 1 in lane 1 and 0 elsewhere, notP = 1 - selP.  The P lane's diagonal
+  // slot, -C until here for the right-hand side above, becomes 1: fma(q, 1, notP) is then q itself, the slot's "pivot" (factor())
+  double selP = isP ? 1.0 : 0.0, notP = isP ? 0.0 : 1.0;
+  if constexpr (PAR) {
+    if (isP) pk.template set<K_DG + 0>(1.0);
+    asm volatile("" : "+v"(selP), "+v"(notP));            // two register pairs, not two selects rebuilt from the lane number in every step
+  }
 
   // Arrow factors of M = I - q J (q = gamma h) for the current step size.
   //   rows: (1 + q B) x_R = r_R ; (1 + q d_i) x_i - q S_i x_P = r_i ; (1 + q Dsum) x_P - q C x_R - q sum x_i = r_P
@@ -497,6 +527,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   // into the group sum) and nothing is inverted on its own.  Row 0 enters that sum as r_0 ws0 with ws0 = winv_0 w0 (C / (1 + q B) | 1 / q |
   // winv_0), and qs = q sinv is the sum's one multiplier.  So that a solve needs no select for the P slot, whose result is x_P itself,
   // lane 1 ends factor() with winv_0 = 0 and cw_0 = 1: fma(cw_0, x_P, r_P winv_0) is x_P (after Scw, to which the slot adds nothing).
+  // Those fix-ups are selects on isP, or, where the registers allow (PAR: dist_pslot_arith()), arithmetic on selP and notP with the same bits:
+  // piv_0 = fma(q, dg_0, notP) with the P lane's dg_0 = 1, cw_0 = fma(winv_0, selP, cw_0), winv_0 = winv_0 notP, omw_0 = fma(omw_0, notP, selP).
   // For the difference stages of LRP8 / LRP12 (below) a row also keeps omw_j = 1 - winv_j, and the lane Cl, the sum of cw over the rows its
   // tracked sum runs over (every site row; resident: rows 1 .. RPL - 1, before the P slot's fixup -- row 0 never enters).  omw is formed as
   // (q winv_j) d_j with d_j the diagonal entry (pivot 1 + q d_j), NOT as 1 - winv_j: on the first steps of a run q d_j is 1e-7 .. 1e-13 and the
@@ -511,8 +543,8 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   //   difference  v'_j = omw_j v_j - cw_j x_P   ->  w'_j = fma(omw_j, w_j, -xq)
   // and the group sum's input sum winv_j v_j is the FMA dot product sum g_j w_j with g_j = winv_j c_j: no product p_j, no add tree, no
   // tracked sum (lam, Cl and the lam - psum cancellation are gone).  The state enters the first solve as rho_j = y_j ic_j with
-  // ic_j = piv_j / s_j (c_j ic_j = 1 to a few ulps), and leaves the step once: y_new_j = fma(c_j, A_j, y_j) with A_j the weighted sum of
-  // the row's w, e_j = c_j w_last,j.  factor() keeps c_j in cw[j]; Scw is q sum c_j, the same number up to rounding, and still what the
+  // ic_j = piv_j / s_j (c_j ic_j = 1 to a few ulps; or as itself, without ic_j: S1, at solve()), and leaves the step once:
+  // y_new_j = fma(c_j, A_j, y_j) with A_j the weighted sum of the row's w, e_j = c_j w_last,j.  factor() keeps c_j in cw[j]; Scw is q sum c_j, the same number up to rounding, and still what the
   // cold non-finite test reads.  Resident: rows 1 .. RPL - 1 are scaled; row 0 (R slot, P slot, two sites) keeps plain units and its explicit
   // term r_0 ws0 in the group sum, but takes xq like the others: cw[0] is cw_0 / q = winv_0 S_0, and in the P slot lane 1's own 1 / q
   // (its chain's result for the "pivot" q), so that fma(cw_0, xq, 0) is x_P; qs = q^2 sinv is then the sum's one multiplier.  Shadowed:
@@ -526,9 +558,10 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
     if constexpr (!RES) piv[0] = __builtin_fma(q, cB, 1.0);
     static_for<RPL>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      piv[X + j] = __builtin_fma(q, pk.template get<K_DG + j>(), 1.0);
+      if constexpr (PAR && j == 0) piv[0] = __builtin_fma(q, pk.template get<K_DG + 0>(), notP);
+      else piv[X + j] = __builtin_fma(q, pk.template get<K_DG + j>(), 1.0);
     });
-    if constexpr (RES) piv[0] = isP ? q : piv[0];
+    if constexpr (RES && !PAR) piv[0] = isP ? q : piv[0];
     {
       double a[M0], inv[M0];
 #pragma unroll
@@ -550,12 +583,13 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       constexpr int j = decltype(jc)::value;
       if constexpr (SCL) {
         // cw[j] is c_j = cw_j / q in every row (the K_SR slot of a scaled row holds its scale s_j)
-        // a scaled row's winv_j ends here: its solves are written with omw_j = 1 - winv_j (solve(), below)
+        // a scaled row's winv_j ends here (S1: at the first dot product, which follows directly): its solves are written with
+        // omw_j = 1 - winv_j (solve(), below)
         cw[j] = winv[j] * pk.template get<K_SR + j>();
         omw[j] = (q * winv[j]) * pk.template get<K_DG + j>();
         if constexpr (j >= J0) {
           g[j] = winv[j] * cw[j];
-          ic[j] = piv[X + j] * is[j];
+          if constexpr (!S1) ic[j] = piv[X + j] * is[j];
         }
       } else if constexpr (Tab::DIFFERENCE) {
         const double qw = q * winv[j];
@@ -587,37 +621,50 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       qs = q * sinv;
       if constexpr (SCL) qs *= q;
       ws0 = winv[0] * w0;
-      if constexpr (SCL) cw[0] = isP ? winv[0] : cw[0]; else cw[0] = isP ? 1.0 : cw[0];
-      winv[0] = isP ? 0.0 : winv[0];
-      if constexpr (Tab::DIFFERENCE) omw[0] = isP ? 1.0 : omw[0];
+      if constexpr (PAR) {
+        // the same 64 bits as the selects below for finite values: the P lane's cw[0] is 0 here (its rate slot is 0) and its winv[0] is
+        // the chain's 1 / q > 0, products with 0 and 1 are exact; a non-finite winv[0] or omw[0] turns NaN here instead of one
+        // operation later, in a step that is rejected either way
+        if constexpr (SCL) cw[0] = __builtin_fma(winv[0], selP, cw[0]); else cw[0] += selP;
+        winv[0] *= notP;
+        if constexpr (Tab::DIFFERENCE) omw[0] = __builtin_fma(omw[0], notP, selP);
+      } else {
+        if constexpr (SCL) cw[0] = isP ? winv[0] : cw[0]; else cw[0] = isP ? 1.0 : cw[0];
+        winv[0] = isP ? 0.0 : winv[0];
+        if constexpr (Tab::DIFFERENCE) omw[0] = isP ? 1.0 : omw[0];
+      }
     }
   };
   // u = M^{-1} r: ONE group reduction.  lam (difference stages): the sum of u over the lane's tracked rows, from the sum of t the solve
   // forms anyway: sum_j u_j = x_P Cl + sum_j t_j
   double lam = 0.0;
-  // Scaled rows: the lane's input to the group sum, sum g_j w_j over its scaled rows as two FMA chains (resident: the first one starts from
-  // row 0's explicit term), and xq = q x_P from it.  Shadowed, the shadow rows' x_R and x_P come back through the arguments
-  auto gdot = [&](const Vec& v) {
+  // Scaled rows: the lane's input to the group sum, sum c_j w_j over its scaled rows as ONE FMA chain (resident: started from row 0's
+  // explicit term), and xq = q x_P from it.  c is g, or winv where the first stage takes the state rows themselves (solve(), below).  The
+  // seven row FMAs of the stage before and the eight accumulation FMAs fill the gaps of the chain at three waves per SIMD: two chains joined
+  // by an add measured 2.3 % slower on the benchmark.  Shadowed, the shadow rows' x_R and x_P come back through the arguments
+  auto gdot = [&](const Vec& v, const double (&c)[RPL]) {
     if constexpr (SCL) {
-      constexpr int H = (RPL + J0) / 2;             // rows [0, H) on the first chain (resident: row 0 by its explicit term), [H, RPL) on the second
-      double a, b = g[H] * v.s[H];
-      if constexpr (RES) a = v.s[0] * ws0; else a = g[0] * v.s[0];
+      double a;
+      if constexpr (RES) a = v.s[0] * ws0; else a = c[0] * v.s[0];
 #pragma unroll
-      for (int j = 1; j < H; ++j) a = __builtin_fma(g[j], v.s[j], a);
-#pragma unroll
-      for (int j = H + 1; j < RPL; ++j) b = __builtin_fma(g[j], v.s[j], b);
-      return a + b;
+      for (int j = 1; j < RPL; ++j) a = __builtin_fma(c[j], v.s[j], a);
+      return a;
     } else return 0.0;
   };
-  auto xq_of = [&](const Vec& v, double& xR, double& xP) {
-    if constexpr (RES) return gsum<G>(gdot(v), lane) * qs;
+  auto xq_of = [&](const Vec& v, const double (&c)[RPL], double& xR, double& xP) {
+    if constexpr (RES) return gsum<G>(gdot(v, c), lane) * qs;
     else {
       xR = v.R() * winvR;
-      xP = __builtin_fma(qq, __builtin_fma(cC, xR, gsum<G>(gdot(v), lane)), v.P()) * sinv;
+      xP = __builtin_fma(qq, __builtin_fma(cC, xR, gsum<G>(gdot(v, c), lane)), v.P()) * sinv;
       return qq * xP;
     }
   };
-  // first (std::true_type: the first stage of a step, scaled rows only): the scaled rows come back as upsilon_j - rho_j, the stage itself
+  // first (std::true_type: the first stage of a step, scaled rows only): the scaled rows come back as upsilon_j - rho_j, the stage itself.
+  // S1 (dist_stage1_state()): r then holds the STATE rows, not rho.  With c_j ic_j = 1 both products the stage needs are known without
+  // ic_j: g_j rho_j = winv_j y_j and omw_j rho_j = q (d_j / s_j) y_j, so with kappa_j = d_j / s_j (is[j], fixed per replica in the prologue)
+  //   t_j = kappa_j y_j ;  dot term fma(winv_j, y_j, .) ;  zeta_j = fma(-q, t_j, xq)
+  // three operations per row where rho takes four (ic_j, rho_j, the dot term, the stage), and the roundings of piv_j / s_j and y_j ic_j are
+  // gone.  A row with s_j = 0 has kappa_j = 0 and zeta_j = xq; its c_j is 0, so every value of the row is still 0 w_j
   auto solve = [&](const Vec& r, auto first) {
     Vec u;
     double xR = 0.0;
@@ -627,12 +674,14 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
       // upsilon_j - rho_j = fma(-omw_j, rho_j, xq) is formed without its cancellation (one operation where the plain rows take two; the
       // second solve pays it back with its add)
       double xP = 0.0;
-      const double xq = xq_of(r, xR, xP);
+      constexpr bool state = S1 && decltype(first)::value;
+      const double xq = state ? xq_of(r, winv, xR, xP) : xq_of(r, g, xR, xP);
       if constexpr (RES) u.s[0] = __builtin_fma(cw[0], xq, r.s[0] * winv[0]);
       else { u.R() = xR; u.P() = xP; }
 #pragma unroll
       for (int j = J0; j < RPL; ++j) {
-        if constexpr (decltype(first)::value) u.s[j] = __builtin_fma(-omw[j], r.s[j], xq);
+        if constexpr (state) u.s[j] = __builtin_fma(-qq, is[j] * r.s[j], xq);
+        else if constexpr (decltype(first)::value) u.s[j] = __builtin_fma(-omw[j], r.s[j], xq);
         else u.s[j] = __builtin_fma(-omw[j], r.s[j], r.s[j] + xq);
       }
       return u;
@@ -676,7 +725,7 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
   auto diff = [&](Vec& v) {
     if constexpr (SCL) {
       double xR = 0.0, xP = 0.0;
-      const double xq = xq_of(v, xR, xP);
+      const double xq = xq_of(v, g, xR, xP);
       if constexpr (RES) v.s[0] = __builtin_fma(-cw[0], xq, omw[0] * v.s[0]);
       else { v.R() *= omwR; v.P() -= xP; }
 #pragma unroll
@@ -782,8 +831,10 @@ __global__ __launch_bounds__(NT, MINB) void dist_fast_kernel(const SolveArgs A) 
         if constexpr (RES) r.s[0] = __builtin_fma(qq, k3, y.s[0]); else r.R() = __builtin_fma(qq, cA, y.R());
         if constexpr (SCL) {
           // the scaled rows enter as rho_j = y_j / c_j, and solve() hands back the first stage upsilon_j - rho_j in the same units
+          if constexpr (!S1) {
 #pragma unroll
-          for (int j = J0; j < RPL; ++j) r.s[j] = y.s[j] * ic[j];
+            for (int j = J0; j < RPL; ++j) r.s[j] = y.s[j] * ic[j];
+          }
           z = solve(r, std::true_type{});
 #pragma unroll
           for (int j = 0; j < Vec::NR; ++j) if (j < J0 || j >= RPL) z.s[j] -= y.s[j];
