@@ -320,6 +320,50 @@ int pk_sobol_build_batch(pk_ctx*, int64_t N, int D, const double* A, const doubl
 int pk_sobol_indices_batch(pk_ctx*, int64_t N, int D, int64_t M, const double* Y, const int32_t* counts, int R,
                            double* S1, double* ST, double* S1_sd, double* ST_sd, double* var);
 
+/* The bookkeeping of a reference-direction many-objective search without a host round trip (reference: pymoo's UNSGA3 with
+ * das-dennis(3, 20) directions, SBX(0.9, 15) and PM(1 / n_var, 10) as built at global_model/runner.py:663-699; pymoo is optional).
+ * global_model/search.py is the generation loop around these four calls; X, F, ranks and niches stay in HBM.  All pointers are device
+ * pointers; the calls are asynchronous on the context's stream, except that pk_moo_rank_batch reads 4 bytes per front.
+ *
+ * Non-dominated ranks of the rows of F [P,M] (M in 2..4, P <= 65536; P = 0 is PK_OK).  Row a dominates row b iff a_m <= b_m for all m and
+ * a_m < b_m for some m; a row with a non-finite entry dominates nothing and is dominated by every all-finite row; two non-finite rows, or
+ * two equal rows, do not dominate each other.  rank = 0 where nothing dominates the row, else 1 + the largest rank among its dominators
+ * (the result of peeling front after front).  n_fronts [1] is the number of fronts formed.  stop_at > 0: peeling stops after the first
+ * front with which at least stop_at rows are ranked, and every row still unranked gets rank = n_fronts; stop_at = 0 ranks every row. */
+int pk_moo_rank_batch(pk_ctx*, int P, int M, const double* F, int stop_at, int32_t* rank, int32_t* n_fronts);
+/* Reference-direction association: f' = (F - ideal) / max(nadir - ideal, 1e-12) per column, dist_h = || f' - (f'.w_h / w_h.w_h) w_h || for
+ * the H <= 4096 rows w_h of dirs [H,M]; niche [P] = argmin_h dist_h (the lowest h among equals), dist [P] = that distance.  A row of F with
+ * a non-finite entry gets niche = -1 and dist = +inf. */
+int pk_moo_associate_batch(pk_ctx*, int P, int M, const double* F, const double* ideal, const double* nadir, int H, const double* dirs,
+                           int32_t* niche, double* dist);
+/* The K survivors of P ranked and associated rows as ascending row indices keep [K] (K > P is an error; K = 0 is PK_OK).  Whole fronts
+ * are taken while they fit.  The first front that does not fit fills the rest by niching: with rho_j the taken rows of niche j, repeatedly
+ * the niche with the smallest rho_j (lowest j among equals) that still has a row of that front gives its row of smallest dist (lowest
+ * index among equals) and rho_j += 1.  Evaluated in closed form: with a_j the rows of that front in niche j and L the largest integer with
+ * sum_j min(a_j, max(0, L - rho_j)) <= the rows still wanted, niche j gives c_j = min(a_j, max(0, L - rho_j)) rows, one more for the
+ * lowest-j niches with rho_j <= L and c_j < a_j until the count is met.  Rows of that front with niche = -1 are taken last, by index.
+ * Within a niche a NaN dist orders after every number (by index among NaNs); pk_moo_associate_batch writes none. */
+int pk_moo_survive_batch(pk_ctx*, int P, int K, const int32_t* rank, const int32_t* niche, const double* dist, int H, int32_t* keep);
+/* Offspring Xc [P,n_var] of the population X [P,n_var]: binary tournament, bounded simulated binary crossover, bounded polynomial
+ * mutation.  Every random number is a function of its coordinates only:
+ *   u(stream, row, var) = (mix(seed + 0x9E3779B97F4A7C15 (1 + ((gen 8 + stream) P + row) n_var + var)) >> 11) 2^-53       (mod 2^64),
+ * mix = the SplitMix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31).
+ *   tournament  slot c: a = floor(u(0, c, 0) P), b = floor(u(1, c, 0) P); the lower rank wins; with equal rank and the same niche the
+ *               smaller dist wins; otherwise a.  parents [P] (optional) = the winner of each slot.  Pair q mates the winners of slots 2 q
+ *               and 2 q + 1 into offspring rows 2 q and 2 q + 1; with odd P the last slot copies its winner (and is then mutated).
+ *   SBX         the pair crosses iff u(2, q, 0) <= pc; variable v of it iff u(3, q, v) <= 0.5, |x1 - x2| > 1e-14 and xu_v > xl_v.  With
+ *               y1 < y2 the two values, u = u(4, q, v) and e = eta_c + 1:  beta = 1 + 2 (y1 - xl) / (y2 - y1), alpha = 2 - beta^-e,
+ *               betaq = (u alpha)^(1/e) if u <= 1 / alpha else (1 / (2 - u alpha))^(1/e), c1 = ((y1 + y2) - betaq (y2 - y1)) / 2; c2 its mirror
+ *               image with beta = 1 + 2 (xu - y2) / (y2 - y1); both clipped to [xl, xu].  Row 2 q gets c1 and row 2 q + 1 gets c2,
+ *               exchanged iff u(5, q, v) <= 0.5.
+ *   PM          offspring row c, variable v mutates iff u(6, c, v) <= pm and xu_v > xl_v.  With u = u(7, c, v), e = eta_m + 1,
+ *               d1 = (x - xl) / (xu - xl), d2 = (xu - x) / (xu - xl):  dq = (2 u + (1 - 2 u) (1 - d1)^e)^(1/e) - 1 for u < 0.5, else
+ *               1 - (2 (1 - u) + 2 (u - 0.5) (1 - d2)^e)^(1/e);  x += dq (xu - xl), clipped.
+ * A value that is neither crossed nor mutated is its parent's, bit for bit. */
+int pk_moo_mate_batch(pk_ctx*, int P, int n_var, const double* X, const int32_t* rank, const int32_t* niche, const double* dist,
+                      const double* xl, const double* xu, uint64_t seed, int gen, double pc, double eta_c, double pm, double eta_m,
+                      double* Xc, int32_t* parents);
+
 /* Replaces config.config.score_fit(params, target, prediction, alpha, beta, gamma, delta, mu) (config/config.py:176-226) for B
  * candidates: theta [B,P], target [N] (shared), pred [B,N] (e.g. the `flat` output) -> out [B].  weights = {alpha (rmse), beta (mae),
  * gamma (var), delta (mse), mu (l2)} as a HOST pointer, NULL = all 1 (config/constants.py:77-83). */

@@ -70,6 +70,7 @@ SYMBOLS = (
     "pk_version", "pk_create", "pk_create_error", "pk_destroy", "pk_last_error", "pk_set_stream", "pk_use_own_stream", "pk_synchronize", "pk_default_opts", "pk_workspace_stats",
     "pk_protein_n_states", "pk_protein_n_params", "pk_protein_flat_len",
     "pk_solve_protein_batch", "pk_solve_protein_sens_batch", "pk_solve_protein_sens_metric_batch", "pk_solve_protein_sens_vjp_batch", "pk_protein_sens_available", "pk_default_fit_opts", "pk_fit_protein_rows_batch", "pk_rhs_protein_batch", "pk_jacobian_protein_batch", "pk_steady_state_protein_batch", "pk_morris_build_batch", "pk_morris_effects_batch", "pk_sobol_build_batch", "pk_sobol_indices_batch", "pk_score_fit_batch",
+    "pk_moo_rank_batch", "pk_moo_associate_batch", "pk_moo_survive_batch", "pk_moo_mate_batch",
     "pk_solve_protein_batch_host", "pk_solve_protein_sens_batch_host", "pk_rhs_protein_batch_host", "pk_jacobian_protein_batch_host",
     "pk_dist_sched_parse", "pk_dist_sched_names", "pk_dist_trace_set",
     "pk_time_solve_protein_batch", "pk_measure_hbm_gbs", "pk_measure_hbm_stream_gbs", "pk_measure_fp64_fma_tflops",
@@ -145,6 +146,11 @@ def load():
     lib.pk_morris_effects_batch.restype = i32; lib.pk_morris_effects_batch.argtypes = [vp, i64, i32, dbl, vp, vp, vp, vp]
     lib.pk_sobol_build_batch.restype = i32; lib.pk_sobol_build_batch.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
     lib.pk_sobol_indices_batch.restype = i32; lib.pk_sobol_indices_batch.argtypes = [vp, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.pk_moo_rank_batch.restype = i32; lib.pk_moo_rank_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    lib.pk_moo_associate_batch.restype = i32; lib.pk_moo_associate_batch.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.pk_moo_survive_batch.restype = i32; lib.pk_moo_survive_batch.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
+    lib.pk_moo_mate_batch.restype = i32
+    lib.pk_moo_mate_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint64, i32, dbl, dbl, dbl, dbl, vp, vp]
     lib.pk_frechet_batch.restype = i32; lib.pk_frechet_batch.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     lib.pk_network_create.restype = vp; lib.pk_network_create.argtypes = [vp, C.POINTER(NetworkDesc)]
     lib.pk_network_destroy.restype = None; lib.pk_network_destroy.argtypes = [vp]

@@ -2,3 +2,4 @@
 batched integration, observables, losses / objectives and the Morris driver."""
 from .engine import NetworkEngine
 from . import config
+from . import search

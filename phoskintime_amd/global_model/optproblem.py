@@ -5,7 +5,7 @@ pool (runner.py:643-645).  Here a whole population ``X [B, n_var]`` (raw decisio
 
     F[b] = (loss_sum_m(b) * norm_m) * lambda_m + prior(b)     for the three modalities m,  or  fail_value where the simulation failed.
 
-``evaluate`` has no pymoo dependency; ``as_pymoo_problem`` wraps it in a vectorised ``pymoo.core.problem.Problem`` when pymoo is installed."""
+``evaluate`` has no pymoo dependency; ``search`` runs the whole generation loop on the device (search.py); ``as_pymoo_problem`` wraps ``evaluate`` in a vectorised ``pymoo.core.problem.Problem`` when pymoo is installed."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -100,6 +100,13 @@ class GlobalODEBatch:
         return _polish.polish_batch(self.eng, self.loss, self.loss_data, X, self.time_grid, cols, lb=lb, ub=ub, obj_w=obj_w, defaults=self.defaults,
                                     lambdas=self.lam, y0=self.y0, raw=True, max_iter=max_iter, driver=driver, rtol=self.rtol, atol=self.atol,
                                     max_steps=self.max_steps * self.time_grid.size, err_norm=self.err_norm, fail_value=self.fail_value, **kw)
+
+    def search(self, pop: int, n_gen: int, seed: int, **kw):
+        """The reference-direction population search of ``search.search`` over this problem's bounds ``xl / xu`` (ValueError without
+        them): Latin-hypercube start, mating, ``evaluate_device``, ranking, association and niching survival all on the device; no
+        pymoo.  Returns its ``SearchResult`` (X, F, rank, niche as GPU tensors, and the per-generation history)."""
+        from . import search as _search
+        return _search.search(self, pop, n_gen, seed, **kw)
 
     def evaluate(self, X) -> np.ndarray:
         """X [B, n_var] raw -> F [B, 3] (host).  Under an initialised ``torch.distributed`` group the candidates are dealt round-robin over
