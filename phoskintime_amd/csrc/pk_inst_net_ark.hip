@@ -14,26 +14,9 @@ size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads) 
   return net_solve_ark_lds_bytes(n, nnzT, rows, threads) + env().ark_lds_pad;
 }
 
-template <int M, int MS>
-static hipError_t launch_one(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {                                  // beyond the default dynamic-LDS limit: raise it per (kernel, device)
-    static std::atomic<uint64_t> ready{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = dev < 64 ? (1ull << dev) : 0;
-    if (!bit || !(ready.load(std::memory_order_acquire) & bit)) {
-      e = hipFuncSetAttribute((const void*)net_solve_ark_kernel<M, MS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      ready.fetch_or(bit, std::memory_order_release);
-    }
-  }
-  hipLaunchKernelGGL((net_solve_ark_kernel<M, MS>), dim3((unsigned)B), dim3(threads), lds, st, n, a);
-  return hipSuccess;
-}
-
-template <int NB, bool EXACT>
-static hipError_t launch_comb(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st) {
+// launch K with `lds` bytes of dynamic LDS; beyond the default limit the limit is raised once per (kernel, device)
+template <void (*K)(const NetDev, const NetSolveArgs)>
+static hipError_t launch_k(const NetDev& n, const NetSolveArgs& a, long long B, int threads, size_t lds, hipStream_t st) {
   if (lds > 64 * 1024) {
     static std::atomic<uint64_t> ready{0};
     int dev = 0;
@@ -41,14 +24,16 @@ static hipError_t launch_comb(const NetDev& n, const NetSolveArgs& a, long long 
     if (e != hipSuccess) return e;
     const uint64_t bit = dev < 64 ? (1ull << dev) : 0;
     if (!bit || !(ready.load(std::memory_order_acquire) & bit)) {
-      e = hipFuncSetAttribute((const void*)net_solve_ark2_kernel<NB, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
       ready.fetch_or(bit, std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL((net_solve_ark2_kernel<NB, EXACT>), dim3((unsigned)B), dim3(threads), lds, st, n, a);
+  hipLaunchKernelGGL(K, dim3((unsigned)B), dim3(threads), lds, st, n, a);
   return hipSuccess;
 }
+template <int M, int MS> static constexpr auto launch_one = launch_k<net_solve_ark_kernel<M, MS>>;
+template <int NB, bool EXACT> static constexpr auto launch_comb = launch_k<net_solve_ark2_kernel<NB, EXACT>>;
 
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st) {
   if (n.model == 2) {

@@ -8,7 +8,6 @@
 #include "pk_network.hpp"
 #include "pk_network_solve.hpp"
 #include "pk_network_solve_reg.hpp"
-#include "pk_network_solve_reg2.hpp"
 #include "pk_network_rk45.hpp"
 #include "pk_network_sens.hpp"
 #include "pk_net_plan.hpp"
@@ -39,6 +38,8 @@ hipError_t launch_net_ws_sens(const NetDev& n, const NetSolveArgs& a, const NetS
 // order-4 additive integrator (pk_network_solve_ark.hpp), its own translation unit: returns the dynamic LDS it needs, or launches
 size_t net_ark_lds_bytes(const NetDev& n, int nnzT, int max_sites, int threads);
 hipError_t launch_net_ark(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
+// register-resident order-3 integrator, one thread per protein (pk_network_solve_reg.hpp, _reg2.hpp; pk_inst_net_reg.hip)
+void launch_net_reg(const NetDev& n, const NetSolveArgs& a, int max_sites, long long B, int threads, size_t lds, hipStream_t st);
 // the same method in the dense two-lanes-per-protein layout (pk_network_solve_arkp.hpp; arrow topologies): n.lane_unit must be set
 bool net_arkp_enabled();
 bool net_arkp_fits(const NetDev& n, int max_sites);
@@ -506,22 +507,9 @@ static int net_simulate_impl(pk_ctx* c, pk_net* n, int64_t B, const double* x, i
       break;
     }
     case NetKernel::CombReg:
-      if (n->max_sites <= 2) hipLaunchKernelGGL((pk::net_solve_reg2_kernel<2>), dim3((unsigned)B), dim3(plan.threads), n->solve_reg_lds_bytes, stream, n->d, a);
-      else                   hipLaunchKernelGGL((pk::net_solve_reg2_kernel<3>), dim3((unsigned)B), dim3(plan.threads), n->solve_reg_lds_bytes, stream, n->d, a);
+    case NetKernel::Reg:
+      pk::launch_net_reg(n->d, a, n->max_sites, (long long)B, plan.threads, n->solve_reg_lds_bytes, stream);
       break;
-    case NetKernel::Reg: {
-      const size_t lb = n->solve_reg_lds_bytes;
-#define PK_REG_LAUNCH(M, MS) hipLaunchKernelGGL((pk::net_solve_reg_kernel<M, MS>), dim3((unsigned)B), dim3(plan.threads), lb, stream, n->d, a)
-      if (n->max_sites <= 4) {
-        if (M == 0) PK_REG_LAUNCH(0, 4); else if (M == 1) PK_REG_LAUNCH(1, 4); else PK_REG_LAUNCH(4, 4);
-      } else if (n->max_sites <= 6) {
-        if (M == 0) PK_REG_LAUNCH(0, 6); else if (M == 1) PK_REG_LAUNCH(1, 6); else PK_REG_LAUNCH(4, 6);
-      } else {
-        if (M == 0) PK_REG_LAUNCH(0, 8); else if (M == 1) PK_REG_LAUNCH(1, 8); else PK_REG_LAUNCH(4, 8);
-      }
-#undef PK_REG_LAUNCH
-      break;
-    }
     case NetKernel::Lds: {
       const int threads = plan.threads;              // every thread owns <= 4 states and <= 2 proteins (register-cached contexts in the kernel)
       if (rosw_fused) {

@@ -45,11 +45,8 @@ __device__ constexpr double EB[6] = {0.0032044943984591762, 0.0, -0.002446251136
 }  // namespace ark436
 
 // LDS parking: thread-private accumulators, slot-major [slot][row][thread] (conflict-free; padding rows are stored like the others: they
-// hold exact zeros).  Slots 0-3: the right-hand sides R_3 .. R_6; with PK_ARK_PARK_SUMS also 4: sum b_j w_j, 5: sum (b_j - bhat_j) w_j.
-#ifndef PK_ARK_PARK_SUMS
-#define PK_ARK_PARK_SUMS 0
-#endif
-constexpr int kArkSlots = PK_ARK_PARK_SUMS ? 6 : 4;
+// hold exact zeros).  Slots 0-3: the right-hand sides R_3 .. R_6.
+constexpr int kArkSlots = 4;
 __host__ __device__ constexpr size_t net_ark_park_doubles(int rows, int threads) { return (size_t)kArkSlots * rows * threads; }
 
 template <int MODEL, int MAXS>
@@ -267,10 +264,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark_kernel(const NetDev n, c
       });
       double sb[NR], se[NR];
 #pragma unroll
-      for (int k = 0; k < NR; ++k) {
-        if constexpr (PK_ARK_PARK_SUMS) { park_st(4, k, B[0] * w[k]); park_st(5, k, EB[0] * w[k]); }
-        else { sb[k] = B[0] * w[k]; se[k] = EB[0] * w[k]; }
-      }
+      for (int k = 0; k < NR; ++k) { sb[k] = B[0] * w[k]; se[k] = EB[0] * w[k]; }
       // ---- stages 2 .. 6.  Register economy: the right-hand side r_s lives only until the solve; h G_s = (Y_s - r_s) / gamma is taken
       // from the scaled right-hand side g r_s as  Y_s / gamma - h (g r_s)  before the stage's f-evaluation, so r_s is dead by then
       static_for<5>([&](auto sc) {
@@ -289,12 +283,7 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark_kernel(const NetDev n, c
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
           w[k] *= hs;
-          if constexpr (s != 2) {                                            // b_2 = bhat_2 = 0
-            if constexpr (PK_ARK_PARK_SUMS) {
-              park_st(4, k, __builtin_fma(B[s - 1], w[k], park_ld(4, k)));
-              park_st(5, k, __builtin_fma(EB[s - 1], w[k], park_ld(5, k)));
-            } else { sb[k] = __builtin_fma(B[s - 1], w[k], sb[k]); se[k] = __builtin_fma(EB[s - 1], w[k], se[k]); }
-          }
+          if constexpr (s != 2) { sb[k] = __builtin_fma(B[s - 1], w[k], sb[k]); se[k] = __builtin_fma(EB[s - 1], w[k], se[k]); }   // b_2 = bhat_2 = 0
         }
         static_for<4>([&](auto ic) {                                         // later right-hand sides take this stage's contribution
           constexpr int ii = decltype(ic)::value;                            // R_{ii + 3}
@@ -304,10 +293,6 @@ __global__ __launch_bounds__(256, 2) void net_solve_ark_kernel(const NetDev n, c
           }
         });
       });
-      if constexpr (PK_ARK_PARK_SUMS) {
-#pragma unroll
-        for (int k = 0; k < NR; ++k) { sb[k] = park_ld(4, k); se[k] = park_ld(5, k); }
-      }
       // ---- new value and error estimate
       auto q = [&](double ev, double ya, double yb) { return fabs(ev) * net_rcp(A.atol + A.rtol * fmax(fabs(ya), fabs(yb))); };
       double e = 0.0;

@@ -8,6 +8,9 @@ a. Forced grid.  rtol = atol = TOL with h0 = 1e9: the kernel takes exactly one s
    the wrong state or the wrong operator moves that ratio by orders of magnitude (the commit that added this file lists them).
 b. Free running.  The four reference-run networks at rtol = atol = 1e-8: accepted and rejected steps within 2 of the restatement's loop,
    band error against LSODA at 1e-12 under the 0.5 of tests/test_gpu_network.py.
+c. Failure exits of the one-thread-per-protein kernels (routes rosw, pair0, sgs, and default on topology 2), on the same free-running
+   grid with the three golden candidates: a NaN parameter flags its candidate alone, and a step budget of half candidate 0's count leaves
+   the rows reached before the exit as they were and NaN after it.
 
 Routes (what net_state_plan resolves them to on these networks is held by tests/test_net_plan_cpu.py; here resolved_method is asserted):
 
@@ -91,6 +94,18 @@ def _golden_x(eng, g, k):
     return eng.pack_params(g["c_k"][k], g["A_i"][k], g["B_i"][k], g["C_i"][k], g["D_i"][k], g["Dp_i"][k], g["E_i"][k], g["tf_scale"][k])
 
 
+def failure_exits(eng, g, kw):
+    """The three golden candidates on the free-running grid, three times: as they are ("clean"), with a NaN in candidate 1's first A_i
+    ("nan"), and on a step budget of half the accepted + rejected steps candidate 0 took in the clean run ("max")."""
+    X = np.stack([_golden_x(eng, g, k) for k in (0, 1, 2)])
+    Xn = X.copy()
+    Xn[1, np.size(g["c_k"][1])] = np.nan                                          # pack_params order: c_k, then A_i
+    run = lambda x, **o: [v.cpu().numpy() for v in eng.simulate_batch(x, g["t_eval"][:FREE_ROWS], y0=g["y0"], rtol=FREE_TOL, atol=FREE_TOL, **kw, **o)]
+    clean = run(X)
+    runs = {"clean": clean, "nan": run(Xn), "max": run(X, max_steps=int(clean[2][0].sum()) // 2)}
+    return {name + k: v for name, r in runs.items() for k, v in zip(("Y", "st", "ns"), r)}
+
+
 def run_routes(out_path, routes, models):
     """Every network of `models` through every route of `routes`, forced grid (all) and free running (the reference-run networks), into
     one .npz.  Runs in this process or, for the switches that are read once per process, in a child."""
@@ -113,6 +128,8 @@ def run_routes(out_path, routes, models):
                 Y, st, ns = eng.simulate_batch(Xg, g["t_eval"][:FREE_ROWS], y0=g["y0"], rtol=FREE_TOL, atol=FREE_TOL, **kw)
                 for k, v in (("freeY", Y), ("freest", st), ("freens", ns)):
                     out["%s/%s/%s" % (route, tag, k)] = v.cpu().numpy()
+                for k, v in failure_exits(eng, g, kw).items():
+                    out["%s/%s/%s" % (route, tag, k)] = v
         eng.close()
     np.savez(out_path, **out)
 
@@ -221,3 +238,39 @@ def test_free_running_step_counts_and_band(gpu, tag, method):
             print("%-18s %-10s %-5s %-5s candidate %d steps %s restatement %s band %.4f" % (tag, route, method, operator, k, got, counts, band))
             assert status == 0 and abs(got[0] - counts[0]) <= 2 and abs(got[1] - counts[1]) <= 2, (tag, route, k, got, counts)
             assert band <= 0.5, (tag, route, k, band)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("tag", nr.GOLDEN_SMALL)
+def test_failure_exits_flag_one_candidate_and_fill_unreached_rows(gpu, tag):
+    """The NONFINITE / MAXSTEPS exits and the NaN fill of the one-thread-per-protein kernels (Reg, CombReg, Ark, ark2): four copies of
+    one stop loop, held to one statement of the rule."""
+    g = np.load(nr.GOLDEN / (tag + ".npz"))
+    routes = [r for r in routes_of(tag) if r in ("rosw", "pair0", "sgs") or (r == "default" and _model(tag) == 2)]
+    assert "rosw" in routes and len(routes) >= 2, routes
+    for route in routes:
+        d = {k: gpu[route]["%s/%s" % (tag, k)] for k in ("cleanY", "cleanst", "cleanns", "nanY", "nanst", "nanns", "maxY", "maxst", "maxns")}
+        Y, st, ns = d["cleanY"], d["cleanst"], d["cleanns"]
+        assert Y.shape[:2] == (3, FREE_ROWS) and not st.any() and np.isfinite(Y).all(), (tag, route, st)
+        y0 = np.ascontiguousarray(np.broadcast_to(g["y0"], Y[:, 0].shape), dtype=np.float64)
+        # (a) a NaN in one A_i of candidate 1
+        assert d["nanst"][1] & nr.ST_NONFINITE, (tag, route, d["nanst"])
+        assert _same_bits(d["nanY"][1, 0], y0[1]) and np.isnan(d["nanY"][1, 1:]).all(), (tag, route)
+        for c in (0, 2):
+            assert _same_bits(d["nanY"][c], Y[c]) and d["nanst"][c] == st[c] and (d["nanns"][c] == ns[c]).all(), (tag, route, c)
+        # (b) max_steps = m, half the clean count of candidate 0
+        m = int(ns[0].sum()) // 2
+        assert m >= 1 and int(ns[0].sum()) > m
+        print("%-18s %-8s clean steps %s budget %d  status %s  steps %s" % (tag, route, ns.tolist(), m, d["maxst"].tolist(), d["maxns"].tolist()))
+        for c in range(3):
+            if int(ns[c].sum()) <= m:                                            # the budget does not bind: the clean run
+                assert _same_bits(d["maxY"][c], Y[c]) and d["maxst"][c] == 0 and (d["maxns"][c] == ns[c]).all(), (tag, route, c)
+                continue
+            assert d["maxst"][c] & nr.ST_MAXSTEPS and int(d["maxns"][c].sum()) == m, (tag, route, c, d["maxst"], d["maxns"])
+            reached = np.isfinite(d["maxY"][c]).all(axis=1)
+            k = int(reached.sum())
+            assert reached[0] and 1 <= k < FREE_ROWS and reached[:k].all() and not reached[k:].any(), (tag, route, c, reached)
+            assert _same_bits(d["maxY"][c, :k], Y[c, :k]) and np.isnan(d["maxY"][c, k:]).all(), (tag, route, c, k)
