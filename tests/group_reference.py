@@ -291,14 +291,21 @@ SIZES = {(pm.DIST, 8): (1, 6), (pm.DIST, 16): (7, 14), (pm.DIST, 32): (15, 30), 
          (pm.RAND, 8): (1, 2), (pm.RAND, 16): (3,), (pm.RAND, 32): (4,), (pm.RAND, 64): (5,)}
 
 
-def case(model, n):
-    """(theta [37, P], y0 [37, S]) of one size: replicas 0-17 from U(0, 20), 18-36 log-uniform on [1e-3, 20]; y0 from U(0.2, 2) per replica."""
+def case(model, n, batch=B):
+    """(theta [37, P], y0 [37, S]) of one size: replicas 0-17 from U(0, 20), 18-36 log-uniform on [1e-3, 20]; y0 from U(0.2, 2) per replica.
+    Another `batch` keeps the proportions (18 in 37 uniform, the rest log-uniform) and is a draw of its own."""
     rng = np.random.default_rng(20261020 + 1000 * model + n)
     P, S = pm.n_params(model, n), pm.n_states(model, n)
-    theta = np.empty((B, P))
-    theta[:18] = rng.uniform(0.0, 20.0, (18, P))
-    theta[18:] = np.exp(rng.uniform(np.log(1e-3), np.log(20.0), (B - 18, P)))
-    return theta, rng.uniform(0.2, 2.0, (B, S))
+    lin = 18 * batch // B
+    theta = np.empty((batch, P))
+    theta[:lin] = rng.uniform(0.0, 20.0, (lin, P))
+    theta[lin:] = np.exp(rng.uniform(np.log(1e-3), np.log(20.0), (batch - lin, P)))
+    return theta, rng.uniform(0.2, 2.0, (batch, S))
+
+
+def compared(batch=B):
+    """The replicas every comparison is made on: first, middle, last (COMPARED at 37)."""
+    return (0, batch // 2, batch - 1)
 
 
 def forced(method, model, theta, n):
@@ -337,3 +344,80 @@ def interval_reference(method, form, sys, rows, t, k, rk4_h=None, dtype=LD):
         hist = [(rows[k - 2], t[k - 1] - t[k - 2]), (rows[k - 3], t[k - 2] - t[k - 3])]
     y, _, maj = one_step(method, form, None, None, None, rows[k - 1], hs, history=hist, dtype=dtype, sys=sys)
     return y, tau(maj)
+
+
+# ------------------------------------------------------------------------------------------------ the randmod and wide-chain kernels
+#: the three groups of environment switches (read once per process: one child process each in tests/test_gpu_rand_matrix.py)
+ENV_TWIN = {"PK_WIDE_RAND_EXACT": "2", "PK_RAND_LEVEL6": "1"}
+ENV_ROWS = {"PK_RAND_PARITY56": "0", "PK_RAND_ROWS": "1"}
+ENV_DEV = {"PK_RAND_PARITY56": "1", "PK_RAND_PARITY6_TB": "16", "PK_RAND_PARITY8_GRID": "512"}
+ENV_GROUPS = ({}, ENV_TWIN, ENV_ROWS, ENV_DEV)
+ALL3 = ("lrp12", "lrp8", "rodas4")
+
+
+class Kernel:
+    """One kernel instantiation outside the lane-group family, and what selects it: `env` (one of ENV_GROUPS) and `kernel` (the
+    solver option, None for "auto"), at batch size B; `plan` is the ProteinKernel protein_plan answers with, `L` the longest accumulation
+    of its linear solve (tests/test_gpu_rand_matrix.py says where each one is read)."""
+
+    def __init__(self, name, model, n, methods, plan, L, env=None, kernel=None, batch=B):
+        self.name, self.model, self.n, self.methods, self.plan, self.L = name, model, n, methods, plan, L
+        self.env, self.kernel, self.B = ENV_GROUPS[0] if env is None else env, kernel, batch
+
+    @property
+    def S(self):
+        return pm.n_states(self.model, self.n)
+
+    def __repr__(self):
+        return "%s n=%d" % (self.name, self.n)
+
+
+def _chain_L(model, n):
+    """distmod: the arrow solve sums the n site rows and the two pivots (S terms); succmod: parallel cyclic reduction adds two terms to
+    a row at each of its ceil(log2 S) levels."""
+    S = n + 2
+    return S if model == pm.DIST else 2 * int(np.ceil(np.log2(S))) + 1
+
+
+#: wide_chain_kernel: the first size past the lane groups, both sides of the launcher's change from 128 to 256 threads (S = 128 | 129), and
+#: the smallest size at which a thread strides over two rows (S = 257 > 256 threads); wide_chain_fits holds up to n = 1276
+CHAIN_SIZES = (63, 126, 127, 255)
+KERNELS = tuple(
+    [Kernel("rand_fast_kernel<%d>" % n, pm.RAND, n, ALL3, "RandFast", 2 ** n) for n in (1, 2)]
+    + [Kernel("rand_fast_kernel<%d>" % n, pm.RAND, n, ALL3, "RandFast", 2 ** n, env=ENV_ROWS) for n in (3, 4, 6)]
+    + [Kernel("rand_fastr_kernel<%d,%d>" % (n, rpl), pm.RAND, n, ALL3, "RandFast", 2 ** n) for n, rpl in ((3, 2), (4, 4), (5, 2))]
+    + [Kernel("tpr_rand_kernel<%d>" % n, pm.RAND, n, ("lrp12",), "Tpr", 2 ** n, kernel="tpr") for n in (1, 2, 3)]
+    + [Kernel("rand_parity_kernel<6,8>", pm.RAND, 6, ("lrp12",), "RandParity", 32),
+       Kernel("rand_parity_kernel<7,16>", pm.RAND, 7, ("lrp12",), "RandParity", 64),
+       Kernel("rand_parity_kernel<7,8>", pm.RAND, 7, ("lrp12",), "RandParity", 64, batch=1024),
+       Kernel("rand_parity_kernel<8,16,16>", pm.RAND, 8, ("lrp12",), "RandParity", 128),
+       Kernel("rand_parity_kernel<5,4>", pm.RAND, 5, ("lrp12",), "RandParity", 16, env=ENV_DEV),
+       Kernel("rand_parity_kernel<6,16>", pm.RAND, 6, ("lrp12",), "RandParity", 32, env=ENV_DEV),
+       Kernel("rand_parity_kernel<8,16,32>", pm.RAND, 8, ("lrp12",), "RandParity", 128, env=ENV_DEV),
+       Kernel("rand_level_kernel<6>", pm.RAND, 6, ("lrp12",), "RandLevel", 20, env=ENV_TWIN),
+       Kernel("rand_level_kernel<8>", pm.RAND, 8, ("lrp12",), "RandLevel", 70, env=ENV_TWIN),
+       Kernel("rand_dense_kernel<7>", pm.RAND, 7, ("lrp12",), "RandDense", 128, env=ENV_TWIN)]
+    + [Kernel("wide_chain_kernel<%s>" % ("M_DIST" if model == pm.DIST else "M_SUCC"), model, n, ("lrp12",), "WideChain", _chain_L(model, n))
+       for model in (pm.DIST, pm.SUCC) for n in CHAIN_SIZES])
+#: every (model, n, batch, method) the table integrates, once
+KERNEL_CASES = tuple(dict.fromkeys((k.model, k.n, k.B, m) for k in KERNELS for m in k.methods))
+#: the double-precision restatement's own |y64 - yld|_inf / tau on the forced grid of each of those cases, worst over the compared
+#: replicas and every row, rounded up to one decimal (tests/test_group_reference_cpu.py measures it and holds it below this figure);
+#: L x this is where a ratio of tests/test_gpu_rand_matrix.py becomes a finding
+KERNEL_R64 = {(pm.RAND, 1, B): (0.6, 1.3, 2.0), (pm.RAND, 2, B): (0.9, 1.2, 2.3), (pm.RAND, 3, B): (2.6, 1.6, 1.8), (pm.RAND, 4, B): (1.5, 2.3, 2.6),
+              (pm.RAND, 5, B): (1.3, 1.3, 2.7), (pm.RAND, 6, B): (2.2, 1.6, 2.7), (pm.RAND, 7, B): (2.2,), (pm.RAND, 7, 1024): (2.2,),
+              (pm.RAND, 8, B): (2.3,), (pm.DIST, 63, B): (2.6,), (pm.DIST, 126, B): (1.9,), (pm.DIST, 127, B): (2.3,), (pm.DIST, 255, B): (2.6,),
+              (pm.SUCC, 63, B): (0.6,), (pm.SUCC, 126, B): (0.9,), (pm.SUCC, 127, B): (1.3,), (pm.SUCC, 255, B): (0.7,)}
+KERNEL_R64 = {(model, n, batch, m): r for (model, n, batch), rs in KERNEL_R64.items() for m, r in zip(ALL3, rs)}
+#: the same figure for the text of tpr_rand_kernel<1> (a 2 x 2 Gauss-Jordan inverse and FMA dot products) evaluated in correctly rounded
+#: double on the CPU, where tests/test_group_reference_cpu.py measures 1.11: the elimination order of that kernel, not LAPACK's
+TPR1_TEXT_R64 = 1.2
+#: runs whose step counts the controller's clamps set (tests/test_gpu_rand_matrix.py, b): GROWTH has err ~ 0, so every step from h0 up to
+#: the grid's spacings grows by the growth clamp's factor 6; SHRINK starts three decades above what its tolerances accept, so its first
+#: 9 to 14 steps are rejected at the shrink clamp's factor 5 and the steps after them go through the after-reject rule
+GROWTH = dict(rtol=1.0, atol=1.0, h0=1e-13)
+SHRINK = dict(rtol=1e-12, atol=1e-14, h0=1e7)
+SHRINK_T = np.array([0.0, 1e6, 2e6])
+#: largest difference in (accepted, rejected) steps of the SHRINK run between a single- and a double-precision root, over KERNEL_CASES' LRP12
+#: cases and the compared replicas (tests/test_group_reference_cpu.py); GROWTH has none: its root is the clamped 1e-30^(1/11) in both
+SHRINK_SPREAD = (2, 1)

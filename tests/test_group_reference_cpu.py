@@ -178,6 +178,178 @@ def test_double_against_long_double_on_the_forced_grids(forced_runs):
         assert v[0] <= R64[k], (k, v)
 
 
+_KERNEL_RUNS = {}
+
+
+def _kernel_forced_run(case):
+    """integrate on the forced grid of one (model, n, batch, method) of gr.KERNEL_CASES, every replica: (t, [(sol, status, n_steps, max err)])."""
+    if case not in _KERNEL_RUNS:
+        model, n, batch, method = case
+        theta, y0 = gr.case(model, n, batch)
+        t, opts = gr.forced(method, model, theta, n)
+        runs = []
+        for b in range(batch):
+            trace = []
+            sol, st, ns = gr.integrate(method, "resolvent", model, theta[b], n, y0[b], t, trace=trace, **opts)
+            runs.append((sol, st, ns, max(e for _, e in trace)))
+        _KERNEL_RUNS[case] = (t, runs)
+    return _KERNEL_RUNS[case]
+
+
+_case_id = lambda c: "%s-n%d-B%d-%s" % (pm.MODEL_NAMES[c[0]], c[1], c[2], c[3])
+
+
+def test_batch_argument_of_case_leaves_the_37_replica_draws_alone():
+    for model, n in ((pm.RAND, 4), (pm.DIST, 62)):
+        a, b = gr.case(model, n), gr.case(model, n, 37)
+        np.testing.assert_array_equal(a[0], b[0])
+        np.testing.assert_array_equal(a[1], b[1])
+        rng = np.random.default_rng(20261020 + 1000 * model + n)                       # the draw as it was written before `batch` existed
+        P = pm.n_params(model, n)
+        np.testing.assert_array_equal(a[0][:18], rng.uniform(0.0, 20.0, (18, P)))
+        np.testing.assert_array_equal(a[0][18:], np.exp(rng.uniform(np.log(1e-3), np.log(20.0), (19, P))))
+        np.testing.assert_array_equal(a[1], rng.uniform(0.2, 2.0, (37, pm.n_states(model, n))))
+    th, y0 = gr.case(pm.RAND, 7, 1024)
+    assert th.shape == (1024, pm.n_params(pm.RAND, 7)) and y0.shape == (1024, 129) and gr.compared(1024) == (0, 512, 1023) and gr.compared() == gr.COMPARED
+
+
+@pytest.mark.parametrize("case", gr.KERNEL_CASES, ids=_case_id)
+def test_kernel_table_forced_grid_is_single_step_and_the_restatement_within_its_cap(case):
+    """The inputs of tests/test_gpu_rand_matrix.py, on every replica of the batch: the restatement accepts exactly one step per interval,
+    rejects none, and its error estimate stays below 0.5 (measured: at most 0.085, distmod n = 255; below 0.007 on randmod) -- so the GPU
+    file's n_steps == (T - 1, 0) is never where this is first learned.  And the double restatement's own |y64 - yld| / tau on the compared
+    replicas stays below the figure recorded in gr.KERNEL_R64, from which the GPU file's finding threshold L x R64 is defined, itself
+    under the cap of 8 that R64 above argues for."""
+    model, n, batch, method = case
+    t, runs = _kernel_forced_run(case)
+    for b, (sol, st, ns, err) in enumerate(runs):
+        assert st == 0 and ns == (t.size - 1, 0) and np.isfinite(sol).all() and err <= 0.5, (case, b, st, ns, err)
+    theta, _ = gr.case(model, n, batch)
+    worst = 0.0
+    for b in gr.compared(batch):
+        sys = gr.system(model, theta[b], n)
+        for k in range(1, t.size):
+            y64, _ = gr.interval_reference(method, "resolvent", sys, runs[b][0], t, k, dtype=float)
+            yld, tt = gr.interval_reference(method, "resolvent", sys, runs[b][0], t, k)
+            worst = max(worst, float(np.max(np.abs(y64 - yld))) / tt)
+    print("kernel table, forced grid:", _case_id(case), "largest err %.4f" % max(r[3] for r in runs), "double against long double %.3f tau" % worst)
+    assert worst <= gr.KERNEL_R64[case] <= R64[method, "resolvent"], (case, worst)
+
+
+def test_kernel_table_step_counts_do_not_hang_on_the_precision_of_the_root():
+    """As test_step_counts_do_not_hang_on_the_precision_of_the_root, at the sizes of gr.KERNEL_CASES: the spread is within ROOT_SPREAD
+    (measured: 1 accepted step of LRP12 at distmod n = 127, 0 everywhere else)."""
+    spread = {m: 0 for m in gr.ROOT_SPREAD}
+    for model, n, batch, method in gr.KERNEL_CASES:
+        theta, y0 = gr.case(model, n, batch)
+        kw = gr.FREE[method, "resolvent"][0]
+        for b in gr.compared(batch):
+            _, s32, n32 = gr.integrate(method, "resolvent", model, theta[b], n, y0[b], pm.TIME_POINTS, root=np.float32, **kw)
+            _, s64, n64 = gr.integrate(method, "resolvent", model, theta[b], n, y0[b], pm.TIME_POINTS, root=np.float64, **kw)
+            assert s32 == 0 and s64 == 0
+            spread[method] = max(spread[method], abs(n32[0] - n64[0]), abs(n32[1] - n64[1]))
+    print("kernel table, steps with a single- against a double-precision root, largest difference:", spread)
+    assert all(spread[m] <= gr.ROOT_SPREAD[m] for m in spread), spread
+
+
+def test_text_of_tpr_rand_kernel_1_in_correctly_rounded_double():
+    """The finding of tests/test_gpu_rand_matrix.py: csrc/pk_tpr_rand.hpp at NB = 1, operation for operation (the 2 x 2 in-place Gauss-Jordan
+    inverse, the mRNA row as a scalar, FMA dot products and FMA stage sums), each operation correctly rounded (exact rational arithmetic,
+    rounded once; the kernel's refined reciprocal taken as 1 / x rounded), on the forced grid from the restatement's rows, against the
+    long-double step.  Measured 1.11 tau where the restatement's LAPACK solve gives 0.59: the figure of this elimination order, recorded
+    as gr.TPR1_TEXT_R64, from which the GPU file's condition for that kernel is defined."""
+    from fractions import Fraction as F
+    fma = lambda a, b, c: float(F(a) * F(b) + F(c))
+    rcp = lambda x: float(1 / F(x))
+    model, n = pm.RAND, 1
+    theta, y0 = gr.case(model, n)
+    t, opts = gr.forced("lrp12", model, theta, n)
+    T = gr.TAB["lrp12"]
+    worst = 0.0
+    for b in gr.COMPARED:
+        th = theta[b]
+        sol, st, _ = gr.integrate("lrp12", "resolvent", model, th, n, y0[b], t, **opts)
+        sys = gr.system(model, th, n)
+        cA, cB, cC, cD, S0, Dd = th
+        dg, ci = [cD + (0.0 + S0), (0.0 + 1.0) + Dd], [0.0, S0]
+        for k in range(1, t.size):
+            hs = t[k] - t[k - 1]
+            yR, y = sol[k - 1][0], list(sol[k - 1][1:])
+            q = T["GAM"] * hs
+            winvR, qC = rcp(fma(q, cB, 1.0)), q * cC
+            a = [[fma(q, dg[0], 1.0), -q * 1.0], [-q * ci[1], fma(q, dg[1], 1.0)]]
+            for kk in range(2):
+                rp, i = rcp(a[kk][kk]), 1 - kk
+                ml = a[i][kk] * rp
+                a[i][i] = fma(-ml, a[kk][i], a[i][i])
+                a[i][kk] = -ml
+                a[kk][i] *= rp
+                a[kk][kk] = rp
+
+            def solve(r, rR):
+                zR = rR * winvR
+                rr = [fma(qC, zR, r[0]), r[1]]
+                return [fma(a[i][1], rr[1], a[i][0] * rr[0]) for i in range(2)], zR
+
+            f = [fma(cC, yR, fma(1.0, y[1], -dg[0] * y[0])) * hs, fma(ci[1], y[0], -dg[1] * y[1]) * hs]
+            z, zR = solve(f, hs * fma(-cB, yR, cA))
+            ynR, yn = fma(T["B"][0], zR, yR), [fma(T["B"][0], z[m], y[m]) for m in range(2)]
+            for s in range(1, len(T["B"])):
+                z, zR = solve(z, zR)
+                ynR, yn = fma(T["B"][s], zR, ynR), [fma(T["B"][s], z[m], yn[m]) for m in range(2)]
+            ref, tt = gr.interval_reference("lrp12", "resolvent", sys, sol, t, k)
+            worst = max(worst, float(np.max(np.abs(np.array([ynR] + yn) - ref.astype(float)))) / tt)
+    print("text of tpr_rand_kernel<1> in correctly rounded double against long double: %.3f tau" % worst)
+    assert gr.KERNEL_R64[model, n, gr.B, "lrp12"] < worst <= gr.TPR1_TEXT_R64 <= R64["lrp12", "resolvent"]
+
+
+def _with_clamps(lo, hi, call):
+    """call() with step_fac's clamps [lo, hi] in group_reference.integrate."""
+    orig = gr.step_fac
+    gr.step_fac = lambda root, lo_=lo, safety_inv=1.0 / 0.9: max(lo_, min(hi, root * safety_inv))
+    try:
+        return call()
+    finally:
+        gr.step_fac = orig
+
+
+def test_clamp_runs_are_set_by_the_clamps_and_not_by_the_precision_of_the_root():
+    """The GROWTH and SHRINK runs of tests/test_gpu_rand_matrix.py on the restatement, at every LRP12 case of the table with up to 129
+    states and on the first replica of the larger ones (what the GPU file compares).  GROWTH: the same count with a single- and a
+    double-precision root, and a growth clamp of 8 instead of 6 takes at least 2 steps fewer -- so the GPU file's equality sees it.  SHRINK:
+    at least 9 rejected steps, the spread between the two roots within SHRINK_SPREAD, and a shrink clamp of 10 instead of 5 rejects at
+    least 2 fewer -- beyond the GPU file's allowance of SHRINK_SPREAD[1] = 1."""
+    spread = [0, 0]
+    for model, n, batch, method in gr.KERNEL_CASES:
+        if method != "lrp12":
+            continue
+        theta, y0 = gr.case(model, n, batch)
+        for b in gr.compared(batch) if pm.n_states(model, n) <= 129 else (0,):
+            run = lambda t, kw, **more: gr.integrate("lrp12", "resolvent", model, theta[b], n, y0[b], t, **kw, **more)[1:]
+            g32, g64 = run(pm.TIME_POINTS, gr.GROWTH), run(pm.TIME_POINTS, gr.GROWTH, root=np.float64)
+            assert g32 == g64 and g32[0] == 0 and g32[1][1] == 0, (model, n, b, g32, g64)
+            s32, s64 = run(gr.SHRINK_T, gr.SHRINK), run(gr.SHRINK_T, gr.SHRINK, root=np.float64)
+            assert s32[0] == 0 and s64[0] == 0 and s32[1][1] >= 9, (model, n, b, s32)
+            for i in (0, 1):
+                spread[i] = max(spread[i], abs(s32[1][i] - s64[1][i]))
+            if pm.n_states(model, n) <= 65:
+                g8 = _with_clamps(1.0 / 8.0, 5.0, lambda: run(pm.TIME_POINTS, gr.GROWTH))
+                s10 = _with_clamps(1.0 / 6.0, 10.0, lambda: run(gr.SHRINK_T, gr.SHRINK))
+                assert g8[1][0] <= g32[1][0] - 2 and s10[1][1] <= s32[1][1] - 2, (model, n, b, g32, g8, s32, s10)
+    print("SHRINK run, single- against double-precision root, largest difference (accepted, rejected):", tuple(spread))
+    assert spread[0] <= gr.SHRINK_SPREAD[0] and spread[1] <= gr.SHRINK_SPREAD[1], spread
+
+
+def test_kernel_table_names_every_kernel_of_the_issue_once():
+    names = [(k.name, k.n) for k in gr.KERNELS]
+    assert len(set(names)) == len(names) == 29
+    assert all(k.env in gr.ENV_GROUPS and "lrp12" == k.methods[0] for k in gr.KERNELS)
+    assert [k.B for k in gr.KERNELS if k.B != gr.B] == [1024]
+    for k in gr.KERNELS:                                                              # wide_chain_lds_bytes of csrc/pk_wide.hpp against the 160 KB of LDS
+        if k.plan == "WideChain":
+            assert (15 * k.S + 2 + k.n + 24) * 8 <= 160 * 1024
+
+
 def test_step_counts_do_not_hang_on_the_precision_of_the_root():
     """The controller's root err^(1/Q) is taken in single precision on the device.  integrate with a single- and with a double-precision
     root on the free-running inputs of the GPU matrix: the spread in accepted / rejected steps is what the GPU file allows the device (plus

@@ -200,6 +200,33 @@ def test_explicit_linsolve_reaches_the_lane_group_kernels_at_every_size_and_swit
                         assert p.structured == (linsolve == STRUCTURED and model != RAND)
 
 
+def test_kernel_table_of_the_rand_matrix_reaches_the_kernels_it_names(shim):
+    """What tests/test_gpu_rand_matrix.py relies on: for every row of group_reference.KERNELS -- its switches, n, B, opts.kernel and each of
+    its methods -- protein_plan answers with the ProteinKernel the row claims.  The plan picks the launcher; which instantiation the
+    launcher then runs (PK_RAND_ROWS, PK_RAND_PARITY6_TB, PK_RAND_PARITY8_GRID, B >= 1024 at n = 7, the thread count of the wide chain)
+    it cannot prove: that part of the table rests on reading launch_rand_fast (csrc/pk_inst_rand_fast.hip) and launch_rand_parity /
+    launch_wide_chain (csrc/pk_inst_wide.hip)."""
+    import group_reference as gr
+    meth = {"lrp12": LRP12, "lrp8": LRP8, "rodas4": RODAS4}
+    for k in gr.KERNELS:
+        sw = dict(exact=int(k.env.get("PK_WIDE_RAND_EXACT", 1)), level6=int(k.env.get("PK_RAND_LEVEL6", 0)), parity56=int(k.env.get("PK_RAND_PARITY56", -1)))
+        assert set(k.env) <= {"PK_WIDE_RAND_EXACT", "PK_RAND_LEVEL6", "PK_RAND_PARITY56", "PK_RAND_ROWS", "PK_RAND_PARITY6_TB", "PK_RAND_PARITY8_GRID"}
+        for method in k.methods:
+            p = plan(shim, k.model, k.n, k.B, method=meth[method], kernel=K_TPR if k.kernel == "tpr" else K_AUTO, **sw)
+            assert (p.kernel, p.code) == (k.plan, OK), (k, method, p.kernel, p.code)
+            assert not p.pinned, k                                    # a pinned family would keep n = 7 on the 256-thread grid at every B
+        # the cut-out replicas of the independence test stay on the same launcher
+        assert plan(shim, k.model, k.n, 1, kernel=K_TPR if k.kernel == "tpr" else K_AUTO, **sw).kernel == k.plan, k
+    # n = 7: the launcher changes instantiation at B = 1024 unless the family is pinned -- the plan's part of that is pinned_family
+    for B in (1023, 1024):
+        assert [plan(shim, RAND, 7, B, kernel=kern).pinned for kern in (K_AUTO, K_GROUP, K_TPR)] == [False, True, True]
+        assert plan(shim, RAND, 7, B).kernel == "RandParity"
+    # n = 6 with LRP8 / RODAS4 is RandFast under every switch group but the level one's LRP12
+    for sw in (dict(), dict(parity56=0), dict(parity56=1), dict(level6=1)):
+        for method in (LRP8, RODAS4):
+            assert plan(shim, RAND, 6, 37, method=method, **sw).kernel == "RandFast"
+
+
 def test_unknown_kernel_and_the_launch_limit(shim):
     for model, n in ((DIST, 4), (SUCC, 8), (RAND, 3), (RAND, 6), (RAND, 9), (DIST, 70)):
         for kern in (K_WORKSPACE, -1):
